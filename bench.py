@@ -1,8 +1,14 @@
 """Benchmark: VAE² ELBO training step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (metric, value,
+unit, higher_is_better, dtype, ms_per_step, ...).  --dump-outputs DIR also writes what the
+last timed step returned (the loss terms and the three predicted clips) as DIR/<name>.npy.
+Everything else the benchmark measures (the roofline / per-family profile, the live
+rocprofv3 passes over the dominant kernel, the CPU baseline) runs only with --full.
 
 Workload (BASELINE.json configs[2], the metric's config): the shipped experiment
 YAML (vae-2_amd/experiments/vae2_w18_small_v2_128x256.yaml) through the drop-in
@@ -18,7 +24,7 @@ same kernels, one launch, bit-identical to eager steps -- tests/test_graph_gpu.p
 N > 1 with the RCCL collectives inside, tests/test_dist_rccl_gpu.py) and replayed; the
 noise is drawn on the device inside the step so every replay samples fresh noise.
 
-Printed JSON also carries:
+With --full the printed JSON also carries:
   roofline      the dominant kernel by time (one instantiation, as rocprofv3 names
                 it), timed live with HIP events around its launches during
                 --roofline-steps eager steps after the timed region (every C-ABI
@@ -54,18 +60,29 @@ YAML = os.path.join(PKG, "experiments", "vae2_w18_small_v2_128x256.yaml")
 METRIC = "training frames/sec on 128x256 8-frame Cityscapes clips, 1/2/4/8 MI355X"
 # ELBO FLOPs per clip at 128x256 (FlopCounterMode over the reference)
 REF_GFLOP_PER_CLIP = {(128, 256): 538.1, (64, 64): 67.27, (32, 32): 16.82, (256, 512): 2152.0}
+DUMP_BYTES = 48 << 20  # --dump-outputs: bytes of array data written in all
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cfg", default=YAML)
     ap.add_argument("--batch", type=int, default=None, help="clips per GPU (YAML: 8)")
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--clip-length", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profiled roofline / per-family "
+                         "phase, the live rocprofv3 passes over the dominant kernel and the "
+                         "CPU baseline (each can be switched off with its --no-* option); a "
+                         "plain run prints the headline line only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (loss terms, predicted "
+                         "clips; rank 0's) as DIR/<name>.npy, float32, at most "
+                         f"{DUMP_BYTES >> 20} MiB in all (a fixed seeded sample of each array "
+                         "beyond that)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=2,
                     help="clips per CPU step (a bounded sample: 1 warm-up + --cpu-steps timed "
@@ -116,7 +133,12 @@ def parse():
                          "steps, tests/test_dist_rccl_gpu.py).  The eager step measured 0-3%% "
                          "faster on an idle host but 10-20%% slower when the host CPUs are "
                          "busy; the graph replay is stable")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.profile_json and not args.full:
+        ap.error("--profile-json is written by the profiled phase: add --full")
+    return args
 
 
 def load_config(args):
@@ -315,6 +337,24 @@ def cpu_baseline(args, config, gpu_batch):
                       f"CPU: {cpu_model()}"}
 
 
+def dump_outputs(dirname, tensors):
+    """Write {name: device tensor} as dirname/<name>.npy (float32).  Within DUMP_BYTES in
+    all the arrays are written whole; beyond it every array keeps the same fraction of its
+    elements, a sample of its flattened form at sorted indices drawn with a fixed seed, so
+    two runs with the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 4 * sum(t.numel() for t in tensors.values())
+    for name, t in tensors.items():
+        a = t.detach().to("cpu", torch.float32).contiguous().numpy()
+        if total > DUMP_BYTES:
+            keep = max(1, a.size * DUMP_BYTES // total)
+            if keep < a.size:
+                idx = np.random.default_rng(0).choice(a.size, size=keep, replace=False)
+                a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -398,16 +438,25 @@ def main():
     xs = [torch.randn(B, 3 * L, H, W, generator=g).to(dev) for _ in range(3)]
     zc = ez.z_dim
 
+    returned = {}  # --dump-outputs: what the step's callee handed back (static under the graph)
+
     def eager_step():
         opt.zero_grad()
         fm.set_noise(torch.randn(B, zc, 1, 1, device=dev), torch.randn(B, zc, 1, 1, device=dev))
-        losses, _, x2p, _ = fm(*xs, 1.0)
+        losses, x1p, x2p, x3p = fm(*xs, 1.0)
+        if args.dump_outputs:
+            names = ("loss_all", "xt_recon", "x2t_recon", "x3t_recon", "z_kl", "gan_seq",
+                     "gan_frame", "xt_hat", "x2t_hat", "x3t_hat")
+            returned.update((k, v.detach()) for k, v in zip(names, (*losses, x1p, x2p, x3p))
+                            if torch.is_tensor(v))
         losses[0].backward()
         vdist.allreduce_grads(opt.flats)
         opt.step()
         if fmd is not None:
             opt_d.zero_grad()
             ld = fmd(xs[1], x2p.detach())[0]
+            if args.dump_outputs:
+                returned["d_loss"] = ld.detach()
             ld.backward()
             vdist.allreduce_grads(opt_d.flats)
             opt_d.step()
@@ -444,10 +493,13 @@ def main():
     vdist.syncbn_check()
     last_loss = float(loss.detach())
 
-    # ---- profiled phase: the same step eager, every C-ABI call timed with HIP events
-    # on its stream, isolated from the side streams ----
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, returned)
+
+    # ---- profiled phase (--full): the same step eager, every C-ABI call timed with HIP
+    # events on its stream, isolated from the side streams ----
     profiler = None
-    if not args.no_roofline and args.roofline_steps > 0:
+    if args.full and not args.no_roofline and args.roofline_steps > 0:
         torch.cuda.synchronize()
         with prof.StepProfiler() as profiler:
             for _ in range(args.roofline_steps):
@@ -560,7 +612,7 @@ def main():
             if args.profile_json:
                 with open(args.profile_json, "w") as f:
                     json.dump(summ, f, indent=1)
-        if world == 1 and not args.no_cpu_baseline and not full:
+        if args.full and world == 1 and not args.no_cpu_baseline and not full:
             out["cpu_baseline"] = cpu_baseline(args, config, B)
         print(json.dumps(out), flush=True)
     if world > 1:
