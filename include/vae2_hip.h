@@ -32,7 +32,7 @@ typedef struct vae2_act {
   int64_t ps; /* pixel stride, in elements */
 } vae2_act;
 
-#define VAE2_ABI_VERSION 12
+#define VAE2_ABI_VERSION 13
 
 int vae2_abi_version(void);
 const char* vae2_last_error(void);
@@ -645,6 +645,28 @@ int vae2_adam_coeffs(double* state, float beta1, float beta2, float* coeffs,
 int vae2_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n,
                        const float* coeffs, float beta1, float beta2, float eps,
                        float weight_decay, void* stream);
+
+/* ABI 13: torch.optim.SGD (the reference's TRAIN.OPTIMIZER sgd, tools/train.py:232-250)
+ * over one flat fp32 buffer, per element:
+ *   g' = g + wd*p (wd != 0) ; momentum != 0: buf = g' on the first step, afterwards
+ *   buf = momentum*buf + (1-dampening)*g' ; d = nesterov ? g' + momentum*buf : buf ;
+ *   momentum == 0: d = g' ; p -= lr*d.                       (maximize is not supported)
+ * buf may be NULL iff momentum == 0.  nesterov needs momentum > 0 and dampening == 0
+ * (torch's rule).  Pointers that are not 16-byte aligned take a scalar path.
+ * vae2_sgd_step is the host-scalar form (first_step selects buf = g').             */
+int vae2_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum,
+                  float dampening, float weight_decay, int nesterov, int first_step,
+                  void* stream);
+
+/* The same step from device memory, for graph replay: state = {step, lr} (double), the
+ * layout of vae2_adam_coeffs.  vae2_sgd_coeffs increments state[0] and writes
+ * coeffs[0..2] = {lr, 1-dampening, step == 1 ? 1 : 0} (float; room for 4), so the first
+ * step is decided on the device and a graph captured before the first step replays
+ * correctly from any step count.  vae2_sgd_step_dev then updates each flat buffer.   */
+int vae2_sgd_coeffs(double* state, float momentum, float dampening, int nesterov,
+                    float* coeffs, void* stream);
+int vae2_sgd_step_dev(float* p, const float* g, float* buf, int64_t n, const float* coeffs,
+                      float momentum, float weight_decay, int nesterov, void* stream);
 
 /* dst = src * scale, for fp32 buffers (grad averaging after all-reduce).       */
 int vae2_scale(float* dst, const float* src, int64_t n, float scale,

@@ -1,4 +1,4 @@
-// ELBO terms, reparameterisation sampler, anomaly check and the Adam step.
+// ELBO terms, reparameterisation sampler, anomaly check and the Adam / SGD steps.
 //
 //   L1Loss (criterion.py:61-69)            -> vae2_l1_fwd / vae2_l1_bwd
 //   KLLoss (criterion.py:72-87) + reparam
@@ -6,6 +6,7 @@
 //   loss assembly (utils.py:150-152)       -> vae2_weighted_sum
 //   _anomoly_detection (utils.py:63-65)    -> vae2_nonfinite_check
 //   torch.optim.Adam (train.py:251-261)    -> vae2_adam_step
+//   torch.optim.SGD (train.py:232-250)     -> vae2_sgd_step
 //   lsgan_adversarial_loss (criterion.py:90-103): MSELoss(sum) vs ones / zeros / batch
 //                                          -> vae2_lsgan_fwd / vae2_lsgan_bwd
 #include "common.h"
@@ -249,6 +250,103 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p,
   }
 }
 
+// torch.optim.SGD.  c = {lr, 1 - dampening, first step ? 1 : 0}: from device memory
+// (sgd_coeffs_kernel, graph replay) or, with coeffs == nullptr, the host's copy.
+struct SgdCoef {
+  float lr, damp1, first;
+};
+
+__global__ void sgd_coeffs_kernel(double* state, float dampening, float* coeffs) {
+  const double step = state[0] + 1.0;
+  state[0] = step;
+  coeffs[0] = (float)state[1];
+  coeffs[1] = (float)(1.0 - (double)dampening);
+  coeffs[2] = step == 1.0 ? 1.f : 0.f;
+}
+
+// One element of the step; b is the momentum buffer's value, read only when MOM and not the
+// first step.  The multiply-adds are written out as fused ones, in torch's operand order, so
+// the 16-byte body and the scalar path give the same bits whatever the compiler would contract.
+template <bool MOM>
+__device__ __forceinline__ void sgd_update(float& p, float g, float& b, const SgdCoef c,
+                                           float momentum, float wd, bool nesterov) {
+  if (wd != 0.f) g = __builtin_fmaf(wd, p, g);
+  float d = g;
+  if (MOM) {
+    b = c.first != 0.f ? g : __builtin_fmaf(c.damp1, g, momentum * b);
+    d = nesterov ? __builtin_fmaf(momentum, b, g) : b;
+  }
+  p = __builtin_fmaf(-c.lr, d, p);
+}
+
+// nq: quads taken with 16-byte accesses (0 when a pointer is not 16-byte aligned); the
+// elements from 4 * nq on take the scalar loop.
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p,
+                                                  const float* __restrict__ g,
+                                                  float* __restrict__ buf, int64_t n,
+                                                  int64_t nq, const float* __restrict__ coeffs,
+                                                  SgdCoef c, float momentum, float wd,
+                                                  int nesterov) {
+  if (coeffs) c = SgdCoef{coeffs[0], coeffs[1], coeffs[2]};
+  const bool nes = nesterov != 0;
+  const bool first = c.first != 0.f;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  f4* p4 = reinterpret_cast<f4*>(p);
+  const f4* g4 = reinterpret_cast<const f4*>(g);
+  f4* b4 = reinterpret_cast<f4*>(buf);
+  for (int64_t i = tid; i < nq; i += stride) {
+    f4 pv = p4[i];
+    const f4 gv = g4[i];
+    f4 bv = {0.f, 0.f, 0.f, 0.f};
+    if (MOM && !first) bv = b4[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float pk = pv[k], bk = bv[k];
+      sgd_update<MOM>(pk, gv[k], bk, c, momentum, wd, nes);
+      pv[k] = pk;
+      bv[k] = bk;
+    }
+    p4[i] = pv;
+    if (MOM) b4[i] = bv;
+  }
+  for (int64_t i = 4 * nq + tid; i < n; i += stride) {
+    float pv = p[i];
+    const float gv = g[i];
+    float bv = 0.f;
+    if (MOM && !first) bv = buf[i];
+    sgd_update<MOM>(pv, gv, bv, c, momentum, wd, nes);
+    p[i] = pv;
+    if (MOM) buf[i] = bv;
+  }
+}
+
+// Argument rules shared by the three SGD entry points (torch.optim.SGD's own).
+inline const char* sgd_args_error(float momentum, float dampening, float wd, int nesterov) {
+  if (!(momentum >= 0.f)) return "momentum must be >= 0";
+  if (!(wd >= 0.f)) return "weight_decay must be >= 0";
+  if (nesterov && (!(momentum > 0.f) || dampening != 0.f))
+    return "nesterov momentum requires a momentum and zero dampening";
+  return nullptr;
+}
+
+inline int sgd_launch(const char* fn, float* p, const float* g, float* buf, int64_t n,
+                      const float* coeffs, SgdCoef c, float momentum, float wd, int nesterov,
+                      void* stream) {
+  if (n == 0) return 0;
+  const uintptr_t bits = (uintptr_t)p | (uintptr_t)g | (uintptr_t)buf;
+  const int64_t nq = (bits & 15) == 0 ? n / 4 : 0;
+  const unsigned nb = ew_blocks(nq ? nq : n, 256, 4096);
+  if (momentum != 0.f)
+    VAE2_LAUNCH(sgd_kernel<true>, dim3(nb), dim3(256), 0, as_stream(stream), p, g, buf, n, nq,
+                coeffs, c, momentum, wd, nesterov);
+  else
+    VAE2_LAUNCH(sgd_kernel<false>, dim3(nb), dim3(256), 0, as_stream(stream), p, g, buf, n, nq,
+                coeffs, c, momentum, wd, nesterov);
+  return check_launch(fn);
+}
+
 __global__ void scale_kernel(float* dst, const float* src, int64_t n, float s) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
@@ -419,6 +517,40 @@ int vae2_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n,
   VAE2_LAUNCH(adam_dev_kernel, dim3(ew_blocks(n, 256, 4096)), dim3(256), 0,
                      as_stream(stream), p, g, m, v, n, coeffs, beta1, beta2, eps, weight_decay);
   return check_launch(fn);
+}
+
+int vae2_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum,
+                  float dampening, float weight_decay, int nesterov, int first_step,
+                  void* stream) {
+  const char* fn = "vae2_sgd_step";
+  VAE2_REQUIRE(p && g && n >= 0, fn, "bad arguments");
+  const char* err = sgd_args_error(momentum, dampening, weight_decay, nesterov);
+  VAE2_REQUIRE(!err, fn, err);
+  VAE2_REQUIRE(buf || momentum == 0.f, fn, "momentum needs a momentum buffer");
+  const SgdCoef c{lr, (float)(1.0 - (double)dampening), first_step ? 1.f : 0.f};
+  return sgd_launch(fn, p, g, buf, n, nullptr, c, momentum, weight_decay, nesterov, stream);
+}
+
+int vae2_sgd_coeffs(double* state, float momentum, float dampening, int nesterov,
+                    float* coeffs, void* stream) {
+  const char* fn = "vae2_sgd_coeffs";
+  VAE2_REQUIRE(state && coeffs, fn, "null pointer");
+  const char* err = sgd_args_error(momentum, dampening, 0.f, nesterov);
+  VAE2_REQUIRE(!err, fn, err);
+  VAE2_LAUNCH(sgd_coeffs_kernel, dim3(1), dim3(1), 0, as_stream(stream), state, dampening,
+              coeffs);
+  return check_launch(fn);
+}
+
+int vae2_sgd_step_dev(float* p, const float* g, float* buf, int64_t n, const float* coeffs,
+                      float momentum, float weight_decay, int nesterov, void* stream) {
+  const char* fn = "vae2_sgd_step_dev";
+  VAE2_REQUIRE(p && g && coeffs && n >= 0, fn, "bad arguments");
+  const char* err = sgd_args_error(momentum, 0.f, weight_decay, nesterov);
+  VAE2_REQUIRE(!err, fn, err);
+  VAE2_REQUIRE(buf || momentum == 0.f, fn, "momentum needs a momentum buffer");
+  return sgd_launch(fn, p, g, buf, n, coeffs, SgdCoef{0.f, 1.f, 0.f}, momentum, weight_decay,
+                    nesterov, stream);
 }
 
 int vae2_scale(float* dst, const float* src, int64_t n, float scale,

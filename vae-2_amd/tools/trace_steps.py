@@ -3,7 +3,8 @@
     python vae-2_amd/tools/trace_steps.py gpurun_out/prof/run_kernel_trace.csv [--steps 10]
         [--instances N] [--json out.json]
 
-Steps are delimited by the Adam launches (the last kernel family of a step).
+Steps are delimited by the Adam launches (the last kernel family of a step); for a
+TRAIN.OPTIMIZER sgd run pass --marker sgd (the FusedSGD launches).
 Reports, over the last --steps steps: wall span, GPU busy time (union of
 kernel intervals across streams), summed kernel time per family (conv fwd /
 dgrad, weight-grad, BatchNorm, heads, fuse/resample, ...), per kernel, and the

@@ -6,11 +6,12 @@
 Flow (reference train.py:55-353): parse args + YAML -> logger -> models (same
 factories, same RNG order) -> process group (RCCL) -> dataset / sampler / loader
 -> FullModel_encdec -> SyncBN statistics + flat-gradient all-reduce (instead of
-DDP) -> Adam -> resume -> epoch loop -> rank-0 checkpoints with the reference's
-file and key names.
+DDP) -> SGD or Adam (TRAIN.OPTIMIZER) -> resume -> epoch loop -> rank-0 checkpoints with
+the reference's file and key names.
 
-Deliberate differences: `TRAIN.OPTIMIZER: sgd` raises a clear ValueError (the
-reference crashes with a TypeError on `p.name`, train.py:234); single-GPU
+Deliberate differences: `TRAIN.OPTIMIZER: sgd` trains (torch.optim.SGD with
+TRAIN.LR / MOMENTUM / WD / NESTEROV over the same two parameter sets as Adam, as
+vae2.optim.FusedSGD; the reference crashes there on `p.name`, train.py:234); single-GPU
 checkpoints are written (the reference calls `.module` on a non-DDP model,
 train.py:322); epochs past END_EPOCH use the main loader when no
 DATASET.EXTRA_TRAIN_SET is given (the reference raises a NameError there);
@@ -39,7 +40,7 @@ from utils.utils import FullModel_D, FullModel_encdec, create_logger
 
 from vae2 import clips
 from vae2 import dist as vdist
-from vae2.optim import FusedAdam
+from vae2.optim import FusedAdam, FusedSGD
 from vae2.trainer import NullWriter, SyntheticClips
 
 
@@ -116,8 +117,8 @@ def main(argv=None):
 
     gpus = list(config.GPUS)
     distributed = len(gpus) > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1
-    if config.TRAIN.OPTIMIZER != "adam":
-        raise ValueError("Only Support ADAM optimizer (the reference's sgd path is broken)")
+    if config.TRAIN.OPTIMIZER not in ("sgd", "adam"):
+        raise ValueError("Only Support SGD and ADAM optimizer")
     extra = config.MODEL.EXTRA
 
     # models, in the reference's construction order (train.py:79-82)
@@ -164,11 +165,18 @@ def main(argv=None):
                               criterion_gan=lsgan_adversarial_loss()).to(device)
         assert model_encdec.D_model_sequence is model_D.D_model_sequence, "Unexpected behavior."
         assert model_encdec.D_model_frame is model_D.D_model_frame, "Unexpected behavior."
-    # Adam over encz + ED ('D_model' excluded) and over the discriminators (train.py:251-261)
+    # SGD or Adam over encz + ED ('D_model' excluded) and over the discriminators
+    # (train.py:232-261)
     nets = [m for m in (encz_model, encdec_model) if m is not None]
-    optimizer = FusedAdam(nets, lr=config.TRAIN.LR)
-    optimizer_D = FusedAdam([D_model_sequence, D_model_frame], lr=config.TRAIN.LR) if use_d \
-        else None
+    if config.TRAIN.OPTIMIZER == "sgd":
+        def make_opt(mods):
+            return FusedSGD(mods, lr=config.TRAIN.LR, momentum=config.TRAIN.MOMENTUM,
+                            weight_decay=config.TRAIN.WD, nesterov=config.TRAIN.NESTEROV)
+    else:
+        def make_opt(mods):
+            return FusedAdam(mods, lr=config.TRAIN.LR)
+    optimizer = make_opt(nets)
+    optimizer_D = make_opt([D_model_sequence, D_model_frame]) if use_d else None
     if vdist.is_dist():  # replicas start identical (DDP's initial broadcast)
         for opt in (optimizer, optimizer_D):
             for f in (opt.flats if opt is not None else []):

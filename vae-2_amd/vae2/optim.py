@@ -1,12 +1,14 @@
-"""Adam over flat parameter buffers (torch.optim.Adam semantics, train.py:251-261).
+"""Adam and SGD over flat parameter buffers (torch.optim semantics, train.py:232-261).
 
-One vae2_adam_step_dev launch per flat buffer; the math follows torch.optim.Adam
-(lerp first moment, L2 weight decay folded into the gradient, bias corrections
-in double).  The step counter and learning rate live in device memory
-(vae2_adam_coeffs advances them), so the whole step can be captured in a HIP
-graph and replayed (vae2.graph.StepGraph); change the learning rate through
-param_groups[0]["lr"] and the next eager step() — or set_lr() between replays.  state_dict() / load_state_dict() use torch.optim.Adam's format
-(per-parameter exp_avg / exp_avg_sq / step) so optimizer checkpoints interchange.
+One vae2_adam_step_dev / vae2_sgd_step_dev launch per flat buffer; the math follows
+torch.optim.Adam (lerp first moment, L2 weight decay folded into the gradient, bias
+corrections in double) and torch.optim.SGD (L2 weight decay, momentum buffer = gradient on
+the first step, dampening, Nesterov).  The step counter and learning rate live in device
+memory (vae2_adam_coeffs / vae2_sgd_coeffs advance them), so the whole step can be captured
+in a HIP graph and replayed (vae2.graph.StepGraph); change the learning rate through
+param_groups[0]["lr"] and the next eager step() — or set_lr() between replays.
+state_dict() / load_state_dict() use torch.optim's formats (per-parameter exp_avg /
+exp_avg_sq / step for Adam, momentum_buffer for SGD) so optimizer checkpoints interchange.
 """
 
 import torch
@@ -16,28 +18,24 @@ from ._lib import call
 from .params import flatten
 
 
-class FusedAdam:
-    def __init__(self, modules, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+class _FusedFlat:
+    """What the fused optimizers share: the flat buffers and weight packs of their modules,
+    the device-resident {step, lr} state, learning-rate sync and zero_grad."""
+
+    def _init_flat(self, modules, lr, n_coeffs):
         if not isinstance(modules, (list, tuple)):
             modules = [modules]
         self.flats = [flatten(m) for m in modules]
         # packed conv weights, refreshed in one launch per model after every update
         self.packs = [ops.PackPlan(m) for m in modules]
         self.lr = float(lr)
-        self.betas = (float(betas[0]), float(betas[1]))
-        self.eps = float(eps)
-        self.weight_decay = float(weight_decay)
         dev = self.flats[0].data.device
         self._state = torch.zeros(2, dtype=torch.float64, device=dev)  # {step, lr}
-        self._coeffs = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._coeffs = torch.zeros(n_coeffs, dtype=torch.float32, device=dev)
         self._dev_lr = None
-        self.exp_avg = [torch.zeros_like(f.data) for f in self.flats]
-        self.exp_avg_sq = [torch.zeros_like(f.data) for f in self.flats]
-        self.param_groups = [{"params": [p for f in self.flats for p in f.params], "lr": self.lr,
-                              "betas": self.betas, "eps": self.eps,
-                              "weight_decay": self.weight_decay, "amsgrad": False,
-                              "maximize": False, "foreach": None, "capturable": False,
-                              "differentiable": False, "fused": None}]
+
+    def _params(self):
+        return [p for f in self.flats for p in f.params]
 
     def zero_grad(self, set_to_none=False):
         streams.join_all()
@@ -63,6 +61,43 @@ class FusedAdam:
             self._state[1].fill_(lr)
             self._dev_lr = lr
 
+    def _slices(self, *bufs):
+        """(index, parameter, its slice of each flat-shaped buffer list) in state_dict order."""
+        idx = 0
+        for k, f in enumerate(self.flats):
+            for p, off in zip(f.params, f.offsets):
+                yield idx, p, [b[k][off:off + p.numel()] for b in bufs]
+                idx += 1
+
+    def _group_dict(self):
+        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
+        group["params"] = list(range(sum(len(f.params) for f in self.flats)))
+        return group
+
+
+def _check_kind(st, want, other, name):
+    """A clear error for a checkpoint of the other optimizer (torch would fail on a key)."""
+    for s in st.values():
+        if other in s and want not in s:
+            raise ValueError(f"{name}.load_state_dict: the state holds '{other}' entries and no "
+                             f"'{want}' (a checkpoint of another optimizer); set "
+                             "TRAIN.OPTIMIZER to the one that wrote it")
+
+
+class FusedAdam(_FusedFlat):
+    def __init__(self, modules, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        self._init_flat(modules, lr, 2)
+        self.betas = (float(betas[0]), float(betas[1]))
+        self.eps = float(eps)
+        self.weight_decay = float(weight_decay)
+        self.exp_avg = [torch.zeros_like(f.data) for f in self.flats]
+        self.exp_avg_sq = [torch.zeros_like(f.data) for f in self.flats]
+        self.param_groups = [{"params": self._params(), "lr": self.lr,
+                              "betas": self.betas, "eps": self.eps,
+                              "weight_decay": self.weight_decay, "amsgrad": False,
+                              "maximize": False, "foreach": None, "capturable": False,
+                              "differentiable": False, "fused": None}]
+
     @torch.no_grad()
     def step(self):
         self._sync_lr()
@@ -80,32 +115,23 @@ class FusedAdam:
     # ---- torch.optim.Adam-compatible checkpoint format ----
     def state_dict(self):
         state = {}
-        idx = 0
         step = float(self.step_count)
-        for f, m, v in zip(self.flats, self.exp_avg, self.exp_avg_sq):
-            for p, off in zip(f.params, f.offsets):
-                n = p.numel()
-                state[idx] = {"step": torch.tensor(step),
-                              "exp_avg": m[off:off + n].view_as(p).clone(),
-                              "exp_avg_sq": v[off:off + n].view_as(p).clone()}
-                idx += 1
-        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
-        group["params"] = list(range(idx))
-        return {"state": state, "param_groups": [group]}
+        for idx, p, (m, v) in self._slices(self.exp_avg, self.exp_avg_sq):
+            state[idx] = {"step": torch.tensor(step),
+                          "exp_avg": m.view_as(p).clone(),
+                          "exp_avg_sq": v.view_as(p).clone()}
+        return {"state": state, "param_groups": [self._group_dict()]}
 
     @torch.no_grad()
     def load_state_dict(self, sd):
         st = sd["state"]
-        idx = 0
+        _check_kind(st, "exp_avg", "momentum_buffer", "FusedAdam")
         steps = []
-        for f, m, v in zip(self.flats, self.exp_avg, self.exp_avg_sq):
-            for p, off in zip(f.params, f.offsets):
-                n = p.numel()
-                if idx in st:
-                    m[off:off + n].copy_(st[idx]["exp_avg"].reshape(-1))
-                    v[off:off + n].copy_(st[idx]["exp_avg_sq"].reshape(-1))
-                    steps.append(int(float(st[idx]["step"])))
-                idx += 1
+        for idx, p, (m, v) in self._slices(self.exp_avg, self.exp_avg_sq):
+            if idx in st:
+                m.copy_(st[idx]["exp_avg"].reshape(-1))
+                v.copy_(st[idx]["exp_avg_sq"].reshape(-1))
+                steps.append(int(float(st[idx]["step"])))
         if steps:
             self.step_count = max(steps)
         g = sd["param_groups"][0]
@@ -115,3 +141,100 @@ class FusedAdam:
         self.eps = g.get("eps", self.eps)
         self.weight_decay = g.get("weight_decay", self.weight_decay)
 
+
+class FusedSGD(_FusedFlat):
+    """torch.optim.SGD (reference train.py:232-250: lr, momentum, weight_decay, nesterov).
+
+    param_groups[0] carries torch's SGD keys for checkpoints and schedulers, but only "lr"
+    is live (re-read at every eager step(), as in FusedAdam): momentum, dampening,
+    weight_decay and nesterov are fixed at construction or by load_state_dict(), and a later
+    edit of those keys is ignored.  load_state_dict() takes momentum buffers for all
+    parameters or for none: one device step counter decides "first step" for every parameter,
+    so a torch state that lacks the buffer of some parameters (ones that never received a
+    gradient) is refused with a ValueError."""
+
+    def __init__(self, modules, lr, momentum=0.0, dampening=0.0, weight_decay=0.0,
+                 nesterov=False):
+        # torch.optim.SGD's own checks and messages, before any buffer is built
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self._init_flat(modules, lr, 4)
+        self.momentum = float(momentum)
+        self.dampening = float(dampening)
+        self.weight_decay = float(weight_decay)
+        self.nesterov = bool(nesterov)
+        # allocated here, not at the first step: that step may be the one a graph captures, and
+        # an allocation inside a capture would be zero-filled again by every replay.  The
+        # kernel does not read it on the first step, and state_dict() shows it only after one
+        # (torch's momentum_buffer appears then)
+        self.momentum_buffer = None
+        if self.momentum != 0:
+            self._buffers()
+        self.param_groups = [{"params": self._params(), "lr": self.lr,
+                              "momentum": self.momentum, "dampening": self.dampening,
+                              "weight_decay": self.weight_decay, "nesterov": self.nesterov,
+                              "maximize": False, "foreach": None, "differentiable": False,
+                              "fused": None}]
+        self._sync_lr()  # the device lr is set before a capture of the very first step
+
+    def _buffers(self):
+        if self.momentum_buffer is None:
+            self.momentum_buffer = [torch.zeros_like(f.data) for f in self.flats]
+        return self.momentum_buffer
+
+    @torch.no_grad()
+    def step(self):
+        self._sync_lr()
+        streams.join_all()
+        s = ops.stream_ptr()
+        bufs = self._buffers() if self.momentum != 0 else [None] * len(self.flats)
+        call("vae2_sgd_coeffs", ops.ptr(self._state), self.momentum, self.dampening,
+             int(self.nesterov), ops.ptr(self._coeffs), s)
+        for f, b in zip(self.flats, bufs):
+            call("vae2_sgd_step_dev", ops.ptr(f.data), ops.ptr(f.grad),
+                 ops.ptr(b) if b is not None else None, f.numel, ops.ptr(self._coeffs),
+                 self.momentum, self.weight_decay, int(self.nesterov), s)
+        for plan in self.packs:
+            plan.bump_versions()
+
+    # ---- torch.optim.SGD-compatible checkpoint format ----
+    def state_dict(self):
+        state = {}
+        if self.momentum_buffer is not None and self.step_count > 0:
+            for idx, p, (b,) in self._slices(self.momentum_buffer):
+                state[idx] = {"momentum_buffer": b.view_as(p).clone()}
+        return {"state": state, "param_groups": [self._group_dict()]}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        st = sd["state"]
+        _check_kind(st, "momentum_buffer", "exp_avg", "FusedSGD")
+        loaded = [i for i, s in st.items() if s.get("momentum_buffer") is not None]
+        n_params = sum(len(f.params) for f in self.flats)
+        if loaded and len(loaded) != n_params:
+            # one device step counter decides "first step" for every parameter
+            raise ValueError(f"FusedSGD.load_state_dict: momentum buffers for {len(loaded)} of "
+                             f"{n_params} parameters (all or none are supported)")
+        if loaded:
+            for idx, p, (b,) in self._slices(self._buffers()):
+                b.copy_(st[idx]["momentum_buffer"].reshape(-1))
+            self.step_count = max(self.step_count, 1)  # the next step is not the first
+        else:
+            self.step_count = 0
+        g = sd["param_groups"][0]
+        grp = self.param_groups[0]
+        for k in ("lr", "momentum", "dampening", "weight_decay", "nesterov"):
+            grp[k] = g.get(k, grp[k])
+        self._sync_lr()
+        self.momentum = float(grp["momentum"])
+        self.dampening = float(grp["dampening"])
+        self.weight_decay = float(grp["weight_decay"])
+        self.nesterov = bool(grp["nesterov"])
+        if self.momentum != 0:
+            self._buffers()

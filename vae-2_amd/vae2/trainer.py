@@ -7,7 +7,7 @@
   SyntheticClips      Cityscapes-shaped clips (3 segments x CLIP_LENGTH RGB frames
                       stacked on channels, cityscapes.py:311-326) for
                       benchmarking and CI; the zip/PNG clips are vae2/clips.py.
-  create_logger, AverageMeter, get_world_size, get_rank   (utils.py)
+  create_logger, AverageMeter, get_world_size, get_rank, adjust_learning_rate   (utils.py)
 """
 import logging
 import math
@@ -57,6 +57,16 @@ def get_rank():
 def dynamic_coeff(max_iters, cur_iters):
     """KL annealing multiplier (utils.py:465-468)."""
     return math.sin((math.pi / 2) * (float(cur_iters) / float(max_iters)))
+
+
+def adjust_learning_rate(optimizer, base_lr, max_iters, cur_iters, power=0.9):
+    """Poly schedule (utils.py:459-463): writes param_groups[0]['lr'] and returns it.  The
+    fused optimizers pick it up at their next eager step(); between graph replays use
+    set_lr().  adversarial_train does not call it (the reference's call is commented out,
+    function.py:525)."""
+    lr = base_lr * ((1 - float(cur_iters) / max_iters) ** power)
+    optimizer.param_groups[0]["lr"] = lr
+    return lr
 
 
 def create_logger(cfg, cfg_name, phase="train"):
