@@ -32,7 +32,7 @@ typedef struct vae2_act {
   int64_t ps; /* pixel stride, in elements */
 } vae2_act;
 
-#define VAE2_ABI_VERSION 13
+#define VAE2_ABI_VERSION 14
 
 int vae2_abi_version(void);
 const char* vae2_last_error(void);
@@ -667,6 +667,45 @@ int vae2_sgd_coeffs(double* state, float momentum, float dampening, int nesterov
                     float* coeffs, void* stream);
 int vae2_sgd_step_dev(float* p, const float* g, float* buf, int64_t n, const float* coeffs,
                       float momentum, float weight_decay, int nesterov, void* stream);
+
+/* ABI 14: global gradient-norm clipping with the semantics of
+ * torch.nn.utils.clip_grad_norm_ (2-norm), on the device, so a captured step replays it.
+ *
+ * vae2_grad_sumsq writes vae2_grad_norm_ws_size(n) (>= 1 for every n >= 0) double partial
+ * sums of g^2 over a flat fp32 buffer of n elements.  The count depends on n alone (the
+ * block count is capped at a fixed value) and no atomics are used, so the reduction order
+ * and the result are the same in every run and process.  Squares and sums are fp64: the
+ * square of an fp32 value is exact there and the summation error (< n * 2^-53 relative) is
+ * far below half an fp32 ulp, so the fp32 norm is determined up to its final rounding.
+ * Every slot is written by every launch (no zeroing needed); g is read only; a pointer
+ * that is not 16-byte aligned takes a scalar path.
+ *
+ * vae2_clip_coeffs sums `count` partials -- those of all flat buffers of one optimizer,
+ * laid end to end -- in a fixed order in fp64 and writes clip[0] = (float)sqrt(sum), the
+ * total norm t, and clip[1] = the coefficient, in fp32 as torch computes it:
+ * c = max_norm / (t + 1e-6f), clip[1] = c > 1 ? 1 : c.  A NaN norm gives a NaN
+ * coefficient, an infinite norm 0.  clip has room for 4 floats; clip[2..3] are reserved
+ * and not written.  max_norm must be > 0 (+inf allowed: the coefficient is then 1).
+ *
+ * vae2_sgd_step_dev_clip / vae2_adam_step_dev_clip are vae2_sgd_step_dev /
+ * vae2_adam_step_dev on the gradient g * clip[1]: the product is rounded to fp32 on its
+ * own (never contracted into the weight-decay multiply-add), so the result equals the
+ * unclipped step on a pre-scaled gradient bit for bit.  g is not modified.
+ *
+ * vae2_scale_dev: x[i] *= clip[1] in place (the second pass of a stand-alone
+ * clip_grad_norm_).  All return -22 before any launch for n < 0, count < 1, a null
+ * pointer, a max_norm that is NaN or <= 0, and whatever the unclipped steps reject.     */
+int64_t vae2_grad_norm_ws_size(int64_t n);
+int vae2_grad_sumsq(const float* g, int64_t n, double* partials, void* stream);
+int vae2_clip_coeffs(const double* partials, int64_t count, float max_norm, float* clip,
+                     void* stream);
+int vae2_sgd_step_dev_clip(float* p, const float* g, float* buf, int64_t n, const float* coeffs,
+                           const float* clip, float momentum, float weight_decay, int nesterov,
+                           void* stream);
+int vae2_adam_step_dev_clip(float* p, const float* g, float* m, float* v, int64_t n,
+                            const float* coeffs, const float* clip, float beta1, float beta2,
+                            float eps, float weight_decay, void* stream);
+int vae2_scale_dev(float* x, int64_t n, const float* clip, void* stream);
 
 /* dst = src * scale, for fp32 buffers (grad averaging after all-reduce).       */
 int vae2_scale(float* dst, const float* src, int64_t n, float scale,

@@ -225,21 +225,36 @@ __global__ void adam_coeffs_kernel(double* state, float b1, float b2, float* coe
   coeffs[1] = (float)sqrt(1.0 - pow((double)b2, step));
 }
 
+// A product rounded to fp32 on its own: never contracted into a multiply-add that follows.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// CLIP: every gradient element is first multiplied by clip[1] (vae2_clip_coeffs), rounded on
+// its own, so the step equals the unclipped one on a pre-scaled gradient bit for bit.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p,
                                                        const float* __restrict__ g,
                                                        float* __restrict__ m,
                                                        float* __restrict__ v, int64_t n,
                                                        const float* __restrict__ coeffs,
+                                                       const float* __restrict__ clip,
                                                        float b1, float b2, float eps, float wd) {
   const float lr_corr = coeffs[0];
   const float bc2_sqrt = coeffs[1];
   const float w1 = 1.f - b1;
   const float w2 = 1.f - b2;
+  float cc = 1.f;
+  if (CLIP) cc = clip[1];
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     float gi = g[i];
+    if (CLIP) gi = mul_rn(gi, cc);
     float pi = p[i];
-    if (wd != 0.f) gi = gi + wd * pi;
+    // (hipcc contracts the unclipped form to this fused multiply-add; with the clip product
+    //  in front it would pair the two multiplies instead and round wd * p on its own)
+    if (wd != 0.f) gi = CLIP ? __builtin_fmaf(wd, pi, gi) : gi + wd * pi;
     float mi = m[i];
     mi = mi + w1 * (gi - mi);
     float vi = v[i] * b2 + w2 * (gi * gi);
@@ -281,14 +296,18 @@ __device__ __forceinline__ void sgd_update(float& p, float g, float& b, const Sg
 
 // nq: quads taken with 16-byte accesses (0 when a pointer is not 16-byte aligned); the
 // elements from 4 * nq on take the scalar loop.
-template <bool MOM>
+// CLIP: the gradient is first multiplied by clip[1], as in adam_dev_kernel<true>.
+template <bool MOM, bool CLIP>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p,
                                                   const float* __restrict__ g,
                                                   float* __restrict__ buf, int64_t n,
                                                   int64_t nq, const float* __restrict__ coeffs,
+                                                  const float* __restrict__ clip,
                                                   SgdCoef c, float momentum, float wd,
                                                   int nesterov) {
   if (coeffs) c = SgdCoef{coeffs[0], coeffs[1], coeffs[2]};
+  float cc = 1.f;
+  if (CLIP) cc = clip[1];
   const bool nes = nesterov != 0;
   const bool first = c.first != 0.f;
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -304,7 +323,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p,
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float pk = pv[k], bk = bv[k];
-      sgd_update<MOM>(pk, gv[k], bk, c, momentum, wd, nes);
+      sgd_update<MOM>(pk, CLIP ? mul_rn(gv[k], cc) : gv[k], bk, c, momentum, wd, nes);
       pv[k] = pk;
       bv[k] = bk;
     }
@@ -316,7 +335,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p,
     const float gv = g[i];
     float bv = 0.f;
     if (MOM && !first) bv = buf[i];
-    sgd_update<MOM>(pv, gv, bv, c, momentum, wd, nes);
+    sgd_update<MOM>(pv, CLIP ? mul_rn(gv, cc) : gv, bv, c, momentum, wd, nes);
     p[i] = pv;
     if (MOM) buf[i] = bv;
   }
@@ -331,20 +350,101 @@ inline const char* sgd_args_error(float momentum, float dampening, float wd, int
   return nullptr;
 }
 
+template <bool CLIP>
 inline int sgd_launch(const char* fn, float* p, const float* g, float* buf, int64_t n,
-                      const float* coeffs, SgdCoef c, float momentum, float wd, int nesterov,
-                      void* stream) {
+                      const float* coeffs, const float* clip, SgdCoef c, float momentum,
+                      float wd, int nesterov, void* stream) {
   if (n == 0) return 0;
   const uintptr_t bits = (uintptr_t)p | (uintptr_t)g | (uintptr_t)buf;
   const int64_t nq = (bits & 15) == 0 ? n / 4 : 0;
   const unsigned nb = ew_blocks(nq ? nq : n, 256, 4096);
   if (momentum != 0.f)
-    VAE2_LAUNCH(sgd_kernel<true>, dim3(nb), dim3(256), 0, as_stream(stream), p, g, buf, n, nq,
-                coeffs, c, momentum, wd, nesterov);
+    VAE2_LAUNCH((sgd_kernel<true, CLIP>), dim3(nb), dim3(256), 0, as_stream(stream), p, g, buf,
+                n, nq, coeffs, clip, c, momentum, wd, nesterov);
   else
-    VAE2_LAUNCH(sgd_kernel<false>, dim3(nb), dim3(256), 0, as_stream(stream), p, g, buf, n, nq,
-                coeffs, c, momentum, wd, nesterov);
+    VAE2_LAUNCH((sgd_kernel<false, CLIP>), dim3(nb), dim3(256), 0, as_stream(stream), p, g, buf,
+                n, nq, coeffs, clip, c, momentum, wd, nesterov);
   return check_launch(fn);
+}
+
+// Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, 2-norm).  The block count
+// depends on n alone, so the summation order -- and the norm -- is the same in every run.
+constexpr int64_t kNormBlocks = 2048;  // 8 blocks of 256 threads per CU
+static unsigned norm_blocks(int64_t n) {
+  int64_t b = ceil_div(n, 256 * 4);
+  if (b > kNormBlocks) b = kNormBlocks;
+  if (b < 1) b = 1;
+  return (unsigned)b;
+}
+
+// partials[block] = sum of g^2 over the block's grid-stride share, in fp64: the square of an
+// fp32 value is exact there and the summation error stays far below half an fp32 ulp of the
+// norm.  Every block writes its slot (no zeroing, no atomics).  nq as in sgd_kernel.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n,
+                                                         int64_t nq,
+                                                         double* __restrict__ partials) {
+  __shared__ double red[4];
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const f4* g4 = reinterpret_cast<const f4*>(g);
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+#pragma unroll 4
+  for (int64_t i = tid; i < nq; i += stride) {
+    const f4 v = g4[i];
+    const double a = (double)v[0], b = (double)v[1], c = (double)v[2], d = (double)v[3];
+    s0 = fma(a, a, s0);
+    s1 = fma(b, b, s1);
+    s2 = fma(c, c, s2);
+    s3 = fma(d, d, s3);
+  }
+  for (int64_t i = 4 * nq + tid; i < n; i += stride) {
+    const double a = (double)g[i];
+    s0 = fma(a, a, s0);
+  }
+  double s = wave_sum_d((s0 + s1) + (s2 + s3));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// clip[0] = the total norm, clip[1] = torch's clip coefficient, both fp32 (single block, fixed
+// order).  A NaN norm gives a NaN coefficient, an infinite one 0.
+__global__ __launch_bounds__(256) void clip_coeffs_kernel(const double* __restrict__ partials,
+                                                          int64_t count, float max_norm,
+                                                          float* __restrict__ clip) {
+  __shared__ double red[4];
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < count; i += 256) s += partials[i];
+  s = wave_sum_d(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float t = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+    const float c = max_norm / (t + 1e-6f);
+    clip[0] = t;
+    clip[1] = c > 1.f ? 1.f : c;
+  }
+}
+
+// x *= clip[1] in place (the second pass of the stand-alone clip_grad_norm_).
+__global__ __launch_bounds__(256) void clip_scale_kernel(float* __restrict__ x, int64_t n,
+                                                         int64_t nq,
+                                                         const float* __restrict__ clip) {
+  const float cc = clip[1];
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  f4* x4 = reinterpret_cast<f4*>(x);
+  for (int64_t i = tid; i < nq; i += stride) {
+    f4 v = x4[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = mul_rn(v[k], cc);
+    x4[i] = v;
+  }
+  for (int64_t i = 4 * nq + tid; i < n; i += stride) x[i] = mul_rn(x[i], cc);
+}
+
+inline const char* max_norm_error(float max_norm) {
+  return max_norm > 0.f ? nullptr : "max_norm must be > 0 (and not NaN)";
 }
 
 __global__ void scale_kernel(float* dst, const float* src, int64_t n, float s) {
@@ -514,8 +614,20 @@ int vae2_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n,
   const char* fn = "vae2_adam_step_dev";
   VAE2_REQUIRE(p && g && m && v && coeffs && n >= 0, fn, "bad arguments");
   if (n == 0) return 0;
-  VAE2_LAUNCH(adam_dev_kernel, dim3(ew_blocks(n, 256, 4096)), dim3(256), 0,
-                     as_stream(stream), p, g, m, v, n, coeffs, beta1, beta2, eps, weight_decay);
+  VAE2_LAUNCH(adam_dev_kernel<false>, dim3(ew_blocks(n, 256, 4096)), dim3(256), 0,
+              as_stream(stream), p, g, m, v, n, coeffs, (const float*)nullptr, beta1, beta2, eps,
+              weight_decay);
+  return check_launch(fn);
+}
+
+int vae2_adam_step_dev_clip(float* p, const float* g, float* m, float* v, int64_t n,
+                            const float* coeffs, const float* clip, float beta1, float beta2,
+                            float eps, float weight_decay, void* stream) {
+  const char* fn = "vae2_adam_step_dev_clip";
+  VAE2_REQUIRE(p && g && m && v && coeffs && clip && n >= 0, fn, "bad arguments");
+  if (n == 0) return 0;
+  VAE2_LAUNCH(adam_dev_kernel<true>, dim3(ew_blocks(n, 256, 4096)), dim3(256), 0,
+              as_stream(stream), p, g, m, v, n, coeffs, clip, beta1, beta2, eps, weight_decay);
   return check_launch(fn);
 }
 
@@ -528,7 +640,8 @@ int vae2_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, flo
   VAE2_REQUIRE(!err, fn, err);
   VAE2_REQUIRE(buf || momentum == 0.f, fn, "momentum needs a momentum buffer");
   const SgdCoef c{lr, (float)(1.0 - (double)dampening), first_step ? 1.f : 0.f};
-  return sgd_launch(fn, p, g, buf, n, nullptr, c, momentum, weight_decay, nesterov, stream);
+  return sgd_launch<false>(fn, p, g, buf, n, nullptr, nullptr, c, momentum, weight_decay,
+                           nesterov, stream);
 }
 
 int vae2_sgd_coeffs(double* state, float momentum, float dampening, int nesterov,
@@ -549,8 +662,52 @@ int vae2_sgd_step_dev(float* p, const float* g, float* buf, int64_t n, const flo
   const char* err = sgd_args_error(momentum, 0.f, weight_decay, nesterov);
   VAE2_REQUIRE(!err, fn, err);
   VAE2_REQUIRE(buf || momentum == 0.f, fn, "momentum needs a momentum buffer");
-  return sgd_launch(fn, p, g, buf, n, coeffs, SgdCoef{0.f, 1.f, 0.f}, momentum, weight_decay,
-                    nesterov, stream);
+  return sgd_launch<false>(fn, p, g, buf, n, coeffs, nullptr, SgdCoef{0.f, 1.f, 0.f}, momentum,
+                           weight_decay, nesterov, stream);
+}
+
+int vae2_sgd_step_dev_clip(float* p, const float* g, float* buf, int64_t n, const float* coeffs,
+                           const float* clip, float momentum, float weight_decay, int nesterov,
+                           void* stream) {
+  const char* fn = "vae2_sgd_step_dev_clip";
+  VAE2_REQUIRE(p && g && coeffs && clip && n >= 0, fn, "bad arguments");
+  const char* err = sgd_args_error(momentum, 0.f, weight_decay, nesterov);
+  VAE2_REQUIRE(!err, fn, err);
+  VAE2_REQUIRE(buf || momentum == 0.f, fn, "momentum needs a momentum buffer");
+  return sgd_launch<true>(fn, p, g, buf, n, coeffs, clip, SgdCoef{0.f, 1.f, 0.f}, momentum,
+                          weight_decay, nesterov, stream);
+}
+
+int64_t vae2_grad_norm_ws_size(int64_t n) { return norm_blocks(n); }
+
+int vae2_grad_sumsq(const float* g, int64_t n, double* partials, void* stream) {
+  const char* fn = "vae2_grad_sumsq";
+  VAE2_REQUIRE(g && partials && n >= 0, fn, "bad arguments");
+  const int64_t nq = ((uintptr_t)g & 15) == 0 ? n / 4 : 0;
+  VAE2_LAUNCH(grad_sumsq_kernel, dim3(norm_blocks(n)), dim3(256), 0, as_stream(stream), g, n,
+              nq, partials);
+  return check_launch(fn);
+}
+
+int vae2_clip_coeffs(const double* partials, int64_t count, float max_norm, float* clip,
+                     void* stream) {
+  const char* fn = "vae2_clip_coeffs";
+  VAE2_REQUIRE(partials && clip && count >= 1, fn, "bad arguments");
+  const char* err = max_norm_error(max_norm);
+  VAE2_REQUIRE(!err, fn, err);
+  VAE2_LAUNCH(clip_coeffs_kernel, dim3(1), dim3(256), 0, as_stream(stream), partials, count,
+              max_norm, clip);
+  return check_launch(fn);
+}
+
+int vae2_scale_dev(float* x, int64_t n, const float* clip, void* stream) {
+  const char* fn = "vae2_scale_dev";
+  VAE2_REQUIRE(x && clip && n >= 0, fn, "bad arguments");
+  if (n == 0) return 0;
+  const int64_t nq = ((uintptr_t)x & 15) == 0 ? n / 4 : 0;
+  VAE2_LAUNCH(clip_scale_kernel, dim3(ew_blocks(nq ? nq : n, 256, 4096)), dim3(256), 0,
+              as_stream(stream), x, n, nq, clip);
+  return check_launch(fn);
 }
 
 int vae2_scale(float* dst, const float* src, int64_t n, float scale,

@@ -53,6 +53,9 @@ _SCHEMA = {
         "CLIP_CACHE": True,       # zip clips: decode once to a uint8 cache, GPU normalisation
         "CLIP_CACHE_DIR": "",     # default <DATASET.ROOT>/.vae2_cache/<list>_<H>x<W>
         "EVAL_SAMPLES": 100,      # prior samples per clip in tools/inference.py (function.py:124)
+        # global gradient 2-norm clipping threshold of both optimizers (FusedAdam / FusedSGD
+        # max_grad_norm; the generator set and the discriminator set each on their own); 0 = off
+        "CLIP_GRAD_NORM": 0.0,
     },
 }
 

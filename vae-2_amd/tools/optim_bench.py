@@ -2,7 +2,7 @@
 W18-small-v2 encoder-decoder's flat parameter buffer (or --numel N).
 
     python vae-2_amd/tools/optim_bench.py [--iters 100] [--warmup 10] [--numel N]
-        [--json out.json]
+        [--clip] [--json out.json]
 
 Times vae2_sgd_step_dev (momentum 0.9, weight decay 1e-4: the TRAIN.OPTIMIZER sgd defaults)
 and vae2_adam_step_dev, alternating, each launch between its own pair of HIP events (SGD's
@@ -12,6 +12,13 @@ prints the median time and the algorithmic byte rate (SGD reads p, g, buf and wr
 20 B per element; Adam reads p, g, m, v and writes p, m, v: 28 B per element).  A buffer of
 this size stays resident in the 256 MiB Infinity Cache between launches, so the rates are
 not HBM rates.
+
+--clip adds, in the same run and alternating with the two unclipped steps (the yardstick):
+the norm pass of gradient clipping (vae2_grad_sumsq + vae2_clip_coeffs between one pair of
+events; it reads g: 4 B per element; vae2_grad_sumsq alone as well) and the two clipped steps (the bytes of the unclipped
+ones).  Next to each measured ratio the output carries the prediction from the byte counts:
+the norm pass 4/20 of SGD's time plus one small launch, the clipped steps level with the
+unclipped ones.  The threshold is +inf (coefficient 1), so the timed values stay in range.
 """
 import argparse
 import json
@@ -23,7 +30,7 @@ import torch
 
 import _init_paths  # noqa: F401
 
-from vae2._lib import call  # noqa: E402
+from vae2._lib import call, load  # noqa: E402
 from vae2.ops import ptr, stream_ptr  # noqa: E402
 
 YAML = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "experiments",
@@ -64,6 +71,8 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--numel", type=int, default=0, help="buffer elements (default: the model's)")
+    ap.add_argument("--clip", action="store_true",
+                    help="also time the gradient-norm pass and the clipped steps")
     ap.add_argument("--json", default="")
     a = ap.parse_args(argv)
     if a.iters < 50:
@@ -95,10 +104,34 @@ def main(argv=None):
     def adam():
         call("vae2_adam_step_dev", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(acoeffs), 0.9, 0.999,
              1e-8, 0.0, s)
-    t_sgd, t_adam = time_launches((sgd, adam), a.iters, a.warmup)
+    fns = [sgd, adam]
+    rows = [("vae2_sgd_step_dev", 20), ("vae2_adam_step_dev", 28)]
+    if a.clip:
+        n_ws = int(load().vae2_grad_norm_ws_size(n))
+        ws = torch.empty(n_ws, dtype=torch.float64, device=dev)
+        clip = torch.zeros(4, device=dev)
+
+        def norm():
+            call("vae2_grad_sumsq", ptr(g), n, ptr(ws), s)
+            call("vae2_clip_coeffs", ptr(ws), n_ws, float("inf"), ptr(clip), s)
+
+        def sgd_clip():
+            call("vae2_sgd_step_dev_clip", ptr(p), ptr(g), ptr(b), n, ptr(coeffs), ptr(clip),
+                 0.9, 1e-4, 0, s)
+
+        def adam_clip():
+            call("vae2_adam_step_dev_clip", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(acoeffs),
+                 ptr(clip), 0.9, 0.999, 1e-8, 0.0, s)
+
+        def sumsq():  # the streaming pass alone: what of the norm pass is not launch cost
+            call("vae2_grad_sumsq", ptr(g), n, ptr(ws), s)
+        fns += [norm, sgd_clip, adam_clip, sumsq]
+        rows += [("vae2_grad_sumsq+vae2_clip_coeffs", 4), ("vae2_sgd_step_dev_clip", 20),
+                 ("vae2_adam_step_dev_clip", 28), ("vae2_grad_sumsq", 4)]
+    times = time_launches(fns, a.iters, a.warmup)
     out = {"numel": n, "iters": a.iters, "sgd_first_step_flag": float(coeffs[2]),
            "sgd_step_counter": float(state[0])}
-    for name, ts, bpe in (("vae2_sgd_step_dev", t_sgd, 20), ("vae2_adam_step_dev", t_adam, 28)):
+    for (name, bpe), ts in zip(rows, times):
         med = statistics.median(ts)
         out[name] = {"median_us": med, "min_us": min(ts), "max_us": max(ts),
                      "bytes": bpe * n, "GBps": bpe * n / med / 1e3}
@@ -106,6 +139,25 @@ def main(argv=None):
               f"{bpe} B/elem  {bpe * n / med / 1e3:8.1f} GB/s")
     ratio = out["vae2_sgd_step_dev"]["median_us"] / out["vae2_adam_step_dev"]["median_us"]
     print(f"  sgd / adam median time: {ratio:.3f}")
+    if a.clip:
+        if float(clip[1]) != 1.0:
+            raise RuntimeError(f"the clip coefficient is {float(clip[1])}, not 1")
+        med = {name: out[name]["median_us"] for name, _ in rows}
+        out["grad_norm"] = float(clip[0])
+        out["ratios"] = {
+            "norm_pass / sgd": {"measured": med[rows[2][0]] / med["vae2_sgd_step_dev"],
+                                "predicted": 4 / 20,
+                                "basis": "4 of SGD's 20 B per element at SGD's rate, plus one "
+                                         "small launch"},
+            "sgd_clip / sgd": {"measured": med["vae2_sgd_step_dev_clip"]
+                               / med["vae2_sgd_step_dev"], "predicted": 1.0,
+                               "basis": "the same bytes, one more multiply per element"},
+            "adam_clip / adam": {"measured": med["vae2_adam_step_dev_clip"]
+                                 / med["vae2_adam_step_dev"], "predicted": 1.0,
+                                 "basis": "the same bytes, one more multiply per element"},
+        }
+        for k, r in out["ratios"].items():
+            print(f"  {k:18s} measured {r['measured']:.3f}  predicted {r['predicted']:.3f}")
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:

@@ -15,6 +15,8 @@ vae2.optim.FusedSGD; the reference crashes there on `p.name`, train.py:234); sin
 checkpoints are written (the reference calls `.module` on a non-DDP model,
 train.py:322); epochs past END_EPOCH use the main loader when no
 DATASET.EXTRA_TRAIN_SET is given (the reference raises a NameError there);
+`MI355X.CLIP_GRAD_NORM t` (t > 0) clips the global gradient 2-norm of each optimizer's
+parameter set to t inside the fused step (0, the default, is off);
 `MI355X.ELBO_ONLY True` drops the two discriminators (the ELBO step alone; the
 reference always builds them and runs the D step); the Cityscapes sequence zips are
 decoded once into a uint8 cache and normalised on the GPU (MI355X.CLIP_CACHE, default),
@@ -119,6 +121,9 @@ def main(argv=None):
     distributed = len(gpus) > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1
     if config.TRAIN.OPTIMIZER not in ("sgd", "adam"):
         raise ValueError("Only Support SGD and ADAM optimizer")
+    if not config.MI355X.CLIP_GRAD_NORM >= 0:
+        raise ValueError("MI355X.CLIP_GRAD_NORM must be >= 0 (0 = off), got {}".format(
+            config.MI355X.CLIP_GRAD_NORM))
     extra = config.MODEL.EXTRA
 
     # models, in the reference's construction order (train.py:79-82)
@@ -168,13 +173,16 @@ def main(argv=None):
     # SGD or Adam over encz + ED ('D_model' excluded) and over the discriminators
     # (train.py:232-261)
     nets = [m for m in (encz_model, encdec_model) if m is not None]
+    # each parameter set is clipped to the threshold on its own, as two clip_grad_norm_ calls
+    clip = float(config.MI355X.CLIP_GRAD_NORM) or None
     if config.TRAIN.OPTIMIZER == "sgd":
         def make_opt(mods):
             return FusedSGD(mods, lr=config.TRAIN.LR, momentum=config.TRAIN.MOMENTUM,
-                            weight_decay=config.TRAIN.WD, nesterov=config.TRAIN.NESTEROV)
+                            weight_decay=config.TRAIN.WD, nesterov=config.TRAIN.NESTEROV,
+                            max_grad_norm=clip)
     else:
         def make_opt(mods):
-            return FusedAdam(mods, lr=config.TRAIN.LR)
+            return FusedAdam(mods, lr=config.TRAIN.LR, max_grad_norm=clip)
     optimizer = make_opt(nets)
     optimizer_D = make_opt([D_model_sequence, D_model_frame]) if use_d else None
     if vdist.is_dist():  # replicas start identical (DDP's initial broadcast)

@@ -159,6 +159,14 @@ _SIGS = {
     "vae2_sgd_step_dev": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_f32, c_f32, c_int, c_vp]),
     "vae2_sgd_step": (c_int, [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_int, c_int,
                               c_vp]),
+    "vae2_grad_norm_ws_size": (c_i64, [c_i64]),
+    "vae2_grad_sumsq": (c_int, [c_vp, c_i64, c_vp, c_vp]),
+    "vae2_clip_coeffs": (c_int, [c_vp, c_i64, c_f32, c_vp, c_vp]),
+    "vae2_sgd_step_dev_clip": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_f32, c_f32, c_int,
+                                       c_vp]),
+    "vae2_adam_step_dev_clip": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_f32, c_f32,
+                                        c_f32, c_f32, c_vp]),
+    "vae2_scale_dev": (c_int, [c_vp, c_i64, c_vp, c_vp]),
     "vae2_scale": (c_int, [c_vp, c_vp, c_i64, c_f32, c_vp]),
     "vae2_syncbn_comm_bytes": (c_i64, [c_int, c_i64]),
     "vae2_syncbn_comm_init": (c_int, [c_int, c_int, c_i64, c_vp, ctypes.POINTER(c_vp)]),
@@ -185,7 +193,7 @@ _SIGS = {
     "vae2_conv2d_set_grouping": (c_int, [c_int]),
 }
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 _lib = None
 
 

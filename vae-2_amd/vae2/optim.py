@@ -9,20 +9,63 @@ in a HIP graph and replayed (vae2.graph.StepGraph); change the learning rate thr
 param_groups[0]["lr"] and the next eager step() — or set_lr() between replays.
 state_dict() / load_state_dict() use torch.optim's formats (per-parameter exp_avg /
 exp_avg_sq / step for Adam, momentum_buffer for SGD) so optimizer checkpoints interchange.
+
+max_grad_norm (both optimizers; None = off, the launches are then exactly the unclipped
+ones) clips the global 2-norm of all flat gradients of the optimizer to that threshold, with
+the semantics of torch.nn.utils.clip_grad_norm_: one vae2_grad_sumsq per flat buffer (fp64
+partial sums, fixed order), one vae2_clip_coeffs, and the *_clip form of the step, which
+multiplies each gradient element by the device-resident coefficient while it reads it (no
+extra write pass; the gradient buffer is not modified).  Norm and coefficient are recomputed
+on the device by every step, so a captured step replays them; grad_norm() returns the
+device value of the last step without synchronising.  In the distributed loop
+allreduce_grads runs before step(), so the norm is that of the reduced gradient and is
+identical on every rank.  clip_grad_norm_ below is the stand-alone, torch-shaped form.
 """
+import math
 
 import torch
 
 from . import ops, streams
-from ._lib import call
+from ._lib import call, load
 from .params import flatten
+
+
+def _clip_threshold(max_norm, what="max_grad_norm"):
+    """None (off) or a float > 0 (inf allowed), else ValueError."""
+    if max_norm is None:
+        return None
+    v = float(max_norm)
+    if math.isnan(v) or v <= 0.0:
+        raise ValueError(f"Invalid {what}: {max_norm} (None, or a float > 0)")
+    return v
+
+
+class _GradNorm:
+    """The device side of global-norm clipping over a list of FlatParams: the fp64 partials
+    of all buffers laid end to end in one workspace, and clip = {norm, coefficient, -, -}.
+    Everything is allocated here, so launch() may run inside a graph capture."""
+
+    def __init__(self, flats):
+        self.flats = flats
+        sizes = [int(load().vae2_grad_norm_ws_size(f.numel)) for f in flats]
+        self.offsets = [sum(sizes[:k]) for k in range(len(sizes))]
+        self.count = sum(sizes)
+        dev = flats[0].data.device
+        self.ws = torch.empty(self.count, dtype=torch.float64, device=dev)
+        self.clip = torch.zeros(4, dtype=torch.float32, device=dev)
+
+    def launch(self, max_norm, s):
+        for f, off in zip(self.flats, self.offsets):
+            call("vae2_grad_sumsq", ops.ptr(f.grad), f.numel, ops.ptr(self.ws[off:]), s)
+        call("vae2_clip_coeffs", ops.ptr(self.ws), self.count, max_norm, ops.ptr(self.clip), s)
 
 
 class _FusedFlat:
     """What the fused optimizers share: the flat buffers and weight packs of their modules,
     the device-resident {step, lr} state, learning-rate sync and zero_grad."""
 
-    def _init_flat(self, modules, lr, n_coeffs):
+    def _init_flat(self, modules, lr, n_coeffs, max_grad_norm=None):
+        self.max_grad_norm = _clip_threshold(max_grad_norm)
         if not isinstance(modules, (list, tuple)):
             modules = [modules]
         self.flats = [flatten(m) for m in modules]
@@ -33,6 +76,16 @@ class _FusedFlat:
         self._state = torch.zeros(2, dtype=torch.float64, device=dev)  # {step, lr}
         self._coeffs = torch.zeros(n_coeffs, dtype=torch.float32, device=dev)
         self._dev_lr = None
+        # allocated here, never in step(): the step may be the one a graph captures
+        self._norm = _GradNorm(self.flats) if self.max_grad_norm is not None else None
+
+    def grad_norm(self):
+        """The total gradient 2-norm of the last step(): a 0-dim device tensor (a view of
+        the device-resident value, no synchronisation).  Needs max_grad_norm."""
+        if self._norm is None:
+            raise RuntimeError("grad_norm(): the optimizer was built with max_grad_norm=None "
+                               "(pass float('inf') to measure without clipping)")
+        return self._norm.clip[0]
 
     def _params(self):
         return [p for f in self.flats for p in f.params]
@@ -85,8 +138,9 @@ def _check_kind(st, want, other, name):
 
 
 class FusedAdam(_FusedFlat):
-    def __init__(self, modules, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        self._init_flat(modules, lr, 2)
+    def __init__(self, modules, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 max_grad_norm=None):
+        self._init_flat(modules, lr, 2, max_grad_norm)
         self.betas = (float(betas[0]), float(betas[1]))
         self.eps = float(eps)
         self.weight_decay = float(weight_decay)
@@ -103,12 +157,19 @@ class FusedAdam(_FusedFlat):
         self._sync_lr()
         streams.join_all()
         s = ops.stream_ptr()
+        if self._norm is not None:
+            self._norm.launch(self.max_grad_norm, s)
         call("vae2_adam_coeffs", ops.ptr(self._state), self.betas[0], self.betas[1],
              ops.ptr(self._coeffs), s)
         for f, m, v in zip(self.flats, self.exp_avg, self.exp_avg_sq):
-            call("vae2_adam_step_dev", ops.ptr(f.data), ops.ptr(f.grad), ops.ptr(m), ops.ptr(v),
-                 f.numel, ops.ptr(self._coeffs), self.betas[0], self.betas[1], self.eps,
-                 self.weight_decay, s)
+            if self._norm is not None:
+                call("vae2_adam_step_dev_clip", ops.ptr(f.data), ops.ptr(f.grad), ops.ptr(m),
+                     ops.ptr(v), f.numel, ops.ptr(self._coeffs), ops.ptr(self._norm.clip),
+                     self.betas[0], self.betas[1], self.eps, self.weight_decay, s)
+            else:
+                call("vae2_adam_step_dev", ops.ptr(f.data), ops.ptr(f.grad), ops.ptr(m),
+                     ops.ptr(v), f.numel, ops.ptr(self._coeffs), self.betas[0], self.betas[1],
+                     self.eps, self.weight_decay, s)
         for plan in self.packs:
             plan.bump_versions()
 
@@ -154,7 +215,7 @@ class FusedSGD(_FusedFlat):
     gradient) is refused with a ValueError."""
 
     def __init__(self, modules, lr, momentum=0.0, dampening=0.0, weight_decay=0.0,
-                 nesterov=False):
+                 nesterov=False, max_grad_norm=None):
         # torch.optim.SGD's own checks and messages, before any buffer is built
         if lr < 0.0:
             raise ValueError(f"Invalid learning rate: {lr}")
@@ -164,7 +225,7 @@ class FusedSGD(_FusedFlat):
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        self._init_flat(modules, lr, 4)
+        self._init_flat(modules, lr, 4, max_grad_norm)
         self.momentum = float(momentum)
         self.dampening = float(dampening)
         self.weight_decay = float(weight_decay)
@@ -194,12 +255,20 @@ class FusedSGD(_FusedFlat):
         streams.join_all()
         s = ops.stream_ptr()
         bufs = self._buffers() if self.momentum != 0 else [None] * len(self.flats)
+        if self._norm is not None:
+            self._norm.launch(self.max_grad_norm, s)
         call("vae2_sgd_coeffs", ops.ptr(self._state), self.momentum, self.dampening,
              int(self.nesterov), ops.ptr(self._coeffs), s)
         for f, b in zip(self.flats, bufs):
-            call("vae2_sgd_step_dev", ops.ptr(f.data), ops.ptr(f.grad),
-                 ops.ptr(b) if b is not None else None, f.numel, ops.ptr(self._coeffs),
-                 self.momentum, self.weight_decay, int(self.nesterov), s)
+            if self._norm is not None:
+                call("vae2_sgd_step_dev_clip", ops.ptr(f.data), ops.ptr(f.grad),
+                     ops.ptr(b) if b is not None else None, f.numel, ops.ptr(self._coeffs),
+                     ops.ptr(self._norm.clip), self.momentum, self.weight_decay,
+                     int(self.nesterov), s)
+            else:
+                call("vae2_sgd_step_dev", ops.ptr(f.data), ops.ptr(f.grad),
+                     ops.ptr(b) if b is not None else None, f.numel, ops.ptr(self._coeffs),
+                     self.momentum, self.weight_decay, int(self.nesterov), s)
         for plan in self.packs:
             plan.bump_versions()
 
@@ -238,3 +307,26 @@ class FusedSGD(_FusedFlat):
         self.nesterov = bool(grp["nesterov"])
         if self.momentum != 0:
             self._buffers()
+
+
+@torch.no_grad()
+def clip_grad_norm_(target, max_norm):
+    """torch.nn.utils.clip_grad_norm_ (2-norm) over flat gradients, for callers with their own
+    loop (for instance expose_grads() + a torch.optim optimizer): `target` is a fused
+    optimizer or a list of FlatParams.  The gradients are scaled in place by
+    min(1, max_norm / (norm + 1e-6)) (vae2_scale_dev); returns the total norm before
+    clipping as a 0-dim device tensor, without synchronising.  Allocates its small workspace
+    per call: inside a captured step use the optimizers' max_grad_norm instead."""
+    max_norm = _clip_threshold(max_norm, "max_norm")
+    if max_norm is None:
+        raise ValueError("Invalid max_norm: None")
+    flats = list(target.flats) if hasattr(target, "flats") else list(target)
+    if not flats:
+        raise ValueError("clip_grad_norm_: no flat gradients")
+    streams.join_all()
+    s = ops.stream_ptr()
+    norm = _GradNorm(flats)
+    norm.launch(max_norm, s)
+    for f in flats:
+        call("vae2_scale_dev", ops.ptr(f.grad), f.numel, ops.ptr(norm.clip), s)
+    return norm.clip[0]

@@ -35,7 +35,7 @@ FAMILIES = (
     ("batchnorm", r"bn_|reduce_then|chan_partials|partials_reduce"),
     ("heads", r"upsum|head_|up_adj"),
     ("fuse_resample", r"upsample|fuse_sum|relu_bwd|copy_act|tile_kernel|spatial_|codemap"),
-    ("optimizer", r"adam|sgd|pack_weight"),
+    ("optimizer", r"adam|sgd|grad_sumsq|clip_coeffs|clip_scale|pack_weight"),
     ("loss_elbo", r"l1_|reparam|weighted_sum|finish_sum|scale_kernel|nonfinite|nchw|nhwc|"
                   r"sqdiff"),
     ("torch_aten", r"at::native|^at::"),

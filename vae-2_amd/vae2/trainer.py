@@ -3,7 +3,11 @@
   adversarial_train   per-epoch loop (function.py:443-553): H2D, ELBO forward,
                       loss reduce, zero_grad / backward / RCCL grad all-reduce /
                       Adam, the discriminator step (FullModel_D, Adam on the D
-                      parameters), meters, PRINT_FREQ logging.
+                      parameters), meters, PRINT_FREQ logging.  With gradient
+                      clipping on (MI355X.CLIP_GRAD_NORM) the PRINT_FREQ points also
+                      check and log the gradient norms: allreduce_grads runs before
+                      step(), so a norm is that of the reduced gradient, identical on
+                      every rank.
   SyntheticClips      Cityscapes-shaped clips (3 segments x CLIP_LENGTH RGB frames
                       stacked on channels, cityscapes.py:311-326) for
                       benchmarking and CI; the zip/PNG clips are vae2/clips.py.
@@ -156,13 +160,22 @@ def adversarial_train(config, epoch, num_epoch, epoch_iters, base_lr, num_iters,
             loss_D.backward()
             vdist.allreduce_grads(optimizer_D.flats)
             optimizer_D.step()
+            stepped_D = True
         else:
+            stepped_D = False
             reduced_loss_D = torch.zeros(1)
             loss_D_sequence = loss_D_frame = 0.0
         if i_iter % config.PRINT_FREQ == 0:
             if getattr(fm, "defer_checks", False):
                 fm.check_anomalies()  # deferred NaN/Inf flag (utils.py:63-65), one sync
             vdist.syncbn_check()  # a timed-out IPC SyncBN exchange raises here
+            # clipping on: the norms of this iteration's steps, checked on every rank
+            grad_norms = [(tag, float(opt.grad_norm().item()))
+                          for tag, opt, ran in (("encdec", optimizer_encdec, True),
+                                                ("D", optimizer_D, stepped_D))
+                          if ran and getattr(opt, "max_grad_norm", None) is not None]
+            for _, val in grad_norms:
+                assert math.isfinite(val), "gradient norm got nan or inf"
         batch_time.update(time.time() - tic)
         tic = time.time()
         ave_loss_D.update(float(reduced_loss_D.item()))
@@ -180,6 +193,10 @@ def adversarial_train(config, epoch, num_epoch, epoch_iters, base_lr, num_iters,
                             f(loss_xt_recon), f(loss_x2t_recon), f(loss_x3t_recon), f(loss_z_KL),
                             f(loss_x2t_gan_sequence), f(loss_x2t_gan_frame))
             logging.info(msg)
+            if grad_norms:
+                logging.info(" ".join("grad_norm_{}: {:.6f}".format(t, v) for t, v in grad_norms))
+                for tag, val in grad_norms:
+                    writer.add_scalar("train_grad_norm_" + tag, val, global_steps)
             for tag, val in (("train_loss_D", print_loss_D),
                              ("train_loss_D_sequence", f(loss_D_sequence)),
                              ("train_loss_D_frame", f(loss_D_frame)),
