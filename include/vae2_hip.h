@@ -32,7 +32,7 @@ typedef struct vae2_act {
   int64_t ps; /* pixel stride, in elements */
 } vae2_act;
 
-#define VAE2_ABI_VERSION 14
+#define VAE2_ABI_VERSION 15
 
 int vae2_abi_version(void);
 const char* vae2_last_error(void);
@@ -706,6 +706,27 @@ int vae2_adam_step_dev_clip(float* p, const float* g, float* m, float* v, int64_
                             const float* coeffs, const float* clip, float beta1, float beta2,
                             float eps, float weight_decay, void* stream);
 int vae2_scale_dev(float* x, int64_t n, const float* clip, void* stream);
+
+/* ABI 15: exponential moving average of the weights over one flat fp32 buffer, with the
+ * semantics of torch.optim.swa_utils.AveragedModel + get_ema_multi_avg_fn(decay):
+ *   first update: ema[i] = p[i] (a bit copy; ema is not read) ;
+ *   afterwards:   ema[i] = fmaf(w, p[i] - ema[i], ema[i]),  w = (float)(1.0 - (double)decay),
+ * one explicit fused multiply-add, so the 16-byte path and the scalar path (pointers that
+ * are not 16-byte aligned, and the last n % 4 elements) give the same bits.  p is read only.
+ * vae2_ema_update is the host-scalar form (first selects the copy).
+ *
+ * The device form, for graph replay: state[0] is the number of updates so far (double;
+ * state has room for 2 doubles).  vae2_ema_coeffs increments it and writes coeffs[0..1] =
+ * {w, state[0] == 1 ? 1 : 0} (float; room for 4), so the first update is decided on the
+ * device and a graph captured before it replays correctly from any count.
+ * vae2_ema_update_dev then updates each flat buffer; for the same w it gives the bits of
+ * vae2_ema_update.  All return -22 before any launch for n < 0, a null pointer, ema == p
+ * and a decay that is NaN, < 0 or >= 1; n == 0 returns 0 without a launch.              */
+int vae2_ema_coeffs(double* state, float decay, float* coeffs, void* stream);
+int vae2_ema_update_dev(float* ema, const float* p, int64_t n, const float* coeffs,
+                        void* stream);
+int vae2_ema_update(float* ema, const float* p, int64_t n, float decay, int first,
+                    void* stream);
 
 /* dst = src * scale, for fp32 buffers (grad averaging after all-reduce).       */
 int vae2_scale(float* dst, const float* src, int64_t n, float scale,

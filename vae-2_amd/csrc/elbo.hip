@@ -7,6 +7,8 @@
 //   _anomoly_detection (utils.py:63-65)    -> vae2_nonfinite_check
 //   torch.optim.Adam (train.py:251-261)    -> vae2_adam_step
 //   torch.optim.SGD (train.py:232-250)     -> vae2_sgd_step
+//   weight EMA (swa_utils.AveragedModel + get_ema_multi_avg_fn; not in the reference)
+//                                          -> vae2_ema_coeffs / vae2_ema_update_dev
 //   lsgan_adversarial_loss (criterion.py:90-103): MSELoss(sum) vs ones / zeros / batch
 //                                          -> vae2_lsgan_fwd / vae2_lsgan_bwd
 #include "common.h"
@@ -367,6 +369,75 @@ inline int sgd_launch(const char* fn, float* p, const float* g, float* buf, int6
   return check_launch(fn);
 }
 
+// Exponential moving average of the weights (torch.optim.swa_utils.AveragedModel with
+// get_ema_multi_avg_fn(decay)).  c = {w = 1 - decay, first update ? 1 : 0}: from device memory
+// (ema_coeffs_kernel, graph replay) or, with coeffs == nullptr, the host's copy.
+struct EmaCoef {
+  float w, first;
+};
+
+// state[0] counts the updates; the weight is rounded once, from the double 1 - decay.
+__global__ void ema_coeffs_kernel(double* state, float decay, float* coeffs) {
+  const double count = state[0] + 1.0;
+  state[0] = count;
+  coeffs[0] = (float)(1.0 - (double)decay);
+  coeffs[1] = count == 1.0 ? 1.f : 0.f;
+}
+
+// lerp(ema, p, w) in torch's form for w < 0.5, used for every w: one explicit fused
+// multiply-add, so the 16-byte body and the scalar path give the same bits.
+__device__ __forceinline__ float ema_update(float e, float p, float w) {
+  return __builtin_fmaf(w, p - e, e);
+}
+
+// First update: ema = p, moved as 32-bit words (the float's bits, whatever they are) and ema
+// is not read.  Afterwards ema += w * (p - ema).  nq as in sgd_kernel; p is read only.
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema,
+                                                         const float* __restrict__ p, int64_t n,
+                                                         int64_t nq,
+                                                         const float* __restrict__ coeffs,
+                                                         EmaCoef c) {
+  if (coeffs) c = EmaCoef{coeffs[0], coeffs[1]};
+  const float w = c.w;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (c.first != 0.f) {
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    u4* e4 = reinterpret_cast<u4*>(ema);
+    const u4* p4 = reinterpret_cast<const u4*>(p);
+    uint32_t* e1 = reinterpret_cast<uint32_t*>(ema);
+    const uint32_t* p1 = reinterpret_cast<const uint32_t*>(p);
+    for (int64_t i = tid; i < nq; i += stride) e4[i] = p4[i];
+    for (int64_t i = 4 * nq + tid; i < n; i += stride) e1[i] = p1[i];
+    return;
+  }
+  f4* e4 = reinterpret_cast<f4*>(ema);
+  const f4* p4 = reinterpret_cast<const f4*>(p);
+  for (int64_t i = tid; i < nq; i += stride) {
+    f4 ev = e4[i];
+    const f4 pv = p4[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ev[k] = ema_update(ev[k], pv[k], w);
+    e4[i] = ev;
+  }
+  for (int64_t i = 4 * nq + tid; i < n; i += stride) ema[i] = ema_update(ema[i], p[i], w);
+}
+
+// Argument rules shared by the EMA entry points.
+inline const char* ema_decay_error(float decay) {
+  return decay >= 0.f && decay < 1.f ? nullptr : "decay must be in [0, 1) (and not NaN)";
+}
+
+inline int ema_launch(const char* fn, float* ema, const float* p, int64_t n,
+                      const float* coeffs, EmaCoef c, void* stream) {
+  if (n == 0) return 0;
+  const uintptr_t bits = (uintptr_t)ema | (uintptr_t)p;
+  const int64_t nq = (bits & 15) == 0 ? n / 4 : 0;
+  VAE2_LAUNCH(ema_update_kernel, dim3(ew_blocks(nq ? nq : n, 256, 4096)), dim3(256), 0,
+              as_stream(stream), ema, p, n, nq, coeffs, c);
+  return check_launch(fn);
+}
+
 // Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, 2-norm).  The block count
 // depends on n alone, so the summation order -- and the norm -- is the same in every run.
 constexpr int64_t kNormBlocks = 2048;  // 8 blocks of 256 threads per CU
@@ -676,6 +747,34 @@ int vae2_sgd_step_dev_clip(float* p, const float* g, float* buf, int64_t n, cons
   VAE2_REQUIRE(buf || momentum == 0.f, fn, "momentum needs a momentum buffer");
   return sgd_launch<true>(fn, p, g, buf, n, coeffs, clip, SgdCoef{0.f, 1.f, 0.f}, momentum,
                           weight_decay, nesterov, stream);
+}
+
+int vae2_ema_coeffs(double* state, float decay, float* coeffs, void* stream) {
+  const char* fn = "vae2_ema_coeffs";
+  VAE2_REQUIRE(state && coeffs, fn, "null pointer");
+  const char* err = ema_decay_error(decay);
+  VAE2_REQUIRE(!err, fn, err);
+  VAE2_LAUNCH(ema_coeffs_kernel, dim3(1), dim3(1), 0, as_stream(stream), state, decay, coeffs);
+  return check_launch(fn);
+}
+
+int vae2_ema_update_dev(float* ema, const float* p, int64_t n, const float* coeffs,
+                        void* stream) {
+  const char* fn = "vae2_ema_update_dev";
+  VAE2_REQUIRE(ema && p && coeffs && n >= 0, fn, "bad arguments");
+  VAE2_REQUIRE(ema != p, fn, "ema and p must be different buffers");
+  return ema_launch(fn, ema, p, n, coeffs, EmaCoef{0.f, 0.f}, stream);
+}
+
+int vae2_ema_update(float* ema, const float* p, int64_t n, float decay, int first,
+                    void* stream) {
+  const char* fn = "vae2_ema_update";
+  VAE2_REQUIRE(ema && p && n >= 0, fn, "bad arguments");
+  VAE2_REQUIRE(ema != p, fn, "ema and p must be different buffers");
+  const char* err = ema_decay_error(decay);
+  VAE2_REQUIRE(!err, fn, err);
+  const EmaCoef c{(float)(1.0 - (double)decay), first ? 1.f : 0.f};
+  return ema_launch(fn, ema, p, n, nullptr, c, stream);
 }
 
 int64_t vae2_grad_norm_ws_size(int64_t n) { return norm_blocks(n); }

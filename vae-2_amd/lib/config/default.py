@@ -56,6 +56,10 @@ _SCHEMA = {
         # global gradient 2-norm clipping threshold of both optimizers (FusedAdam / FusedSGD
         # max_grad_norm; the generator set and the discriminator set each on their own); 0 = off
         "CLIP_GRAD_NORM": 0.0,
+        # decay of the exponential moving average of the generator weights, kept on the device
+        # by the fused step (FusedAdam / FusedSGD ema_decay), in [0, 1); 0 = off
+        "EMA_DECAY": 0.0,
+        "EVAL_EMA": False,        # tools/inference.py: evaluate the checkpoint's averaged weights
     },
 }
 

@@ -8,6 +8,8 @@ Same flow: config -> logger -> models (encz skipped for DETERMINISTIC) -> clips 
 fixed window (random_pos=False) in list order -> FullModel_encdec -> the encdec
 checkpoint of the training run when TRAIN.RESUME -> core.function.inference for epoch 0
 under no_grad (MI355X.EVAL_SAMPLES prior samples per clip, 100 as the reference).
+MI355X.EVAL_EMA True evaluates the averaged weights of a run trained with
+MI355X.EMA_DECAY > 0 (the checkpoint's "ema_state_dict") instead of the live ones.
 """
 import argparse
 import os
@@ -64,9 +66,18 @@ def main(argv=None):
         if os.path.isfile(state_file):
             ck = torch.load(state_file, map_location="cpu", weights_only=True)
             # the training checkpoint may hold the discriminators' keys (GAN runs)
-            sd = {k: v for k, v in ck["state_dict"].items() if not k.startswith("D_model")}
+            key = "ema_state_dict" if config.MI355X.EVAL_EMA else "state_dict"
+            if key not in ck:
+                raise ValueError("MI355X.EVAL_EMA True needs a checkpoint written with "
+                                 "MI355X.EMA_DECAY > 0: {} holds no 'ema_state_dict'".format(
+                                     state_file))
+            sd = {k: v for k, v in ck[key].items() if not k.startswith("D_model")}
             model_encdec.load_state_dict(sd)
-            logger.info("=> loaded checkpoint (epoch {})".format(ck["epoch"]))
+            if config.MI355X.EVAL_EMA:
+                logger.info("=> loaded EMA weights (epoch {}, {} updates)".format(
+                    ck["epoch"], ck["ema_updates"]))
+            else:
+                logger.info("=> loaded checkpoint (epoch {})".format(ck["epoch"]))
     writer_dict = {"writer": NullWriter(), "train_global_steps": 0, "valid_global_steps": 0}
     return inference(config, 0, config.TRAIN.END_EPOCH, epoch_iters, config.TRAIN.LR,
                      config.TRAIN.END_EPOCH * epoch_iters, loader, None, None, model_encdec,

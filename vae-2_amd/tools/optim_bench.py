@@ -2,7 +2,7 @@
 W18-small-v2 encoder-decoder's flat parameter buffer (or --numel N).
 
     python vae-2_amd/tools/optim_bench.py [--iters 100] [--warmup 10] [--numel N]
-        [--clip] [--json out.json]
+        [--clip] [--ema] [--json out.json]
 
 Times vae2_sgd_step_dev (momentum 0.9, weight decay 1e-4: the TRAIN.OPTIMIZER sgd defaults)
 and vae2_adam_step_dev, alternating, each launch between its own pair of HIP events (SGD's
@@ -19,6 +19,14 @@ events; it reads g: 4 B per element; vae2_grad_sumsq alone as well) and the two 
 ones).  Next to each measured ratio the output carries the prediction from the byte counts:
 the norm pass 4/20 of SGD's time plus one small launch, the clipped steps level with the
 unclipped ones.  The threshold is +inf (coefficient 1), so the timed values stay in range.
+
+--ema adds, in the same run and alternating with the two steps: the weight-average update as
+the optimizers launch it (vae2_ema_coeffs + vae2_ema_update_dev between one pair of events; it
+reads p and ema and writes ema: 12 B per element), vae2_ema_update_dev alone (what of the
+pair is not the small launch) and the first-update form (vae2_ema_update with first = 1, a
+copy: 8 B per element).  Predictions from the byte counts: 12/28 of Adam's time and 12/20 of
+SGD's, plus one small launch.  The tool checks that the timed device-form launches were not
+first updates.
 """
 import argparse
 import json
@@ -73,6 +81,8 @@ def main(argv=None):
     ap.add_argument("--numel", type=int, default=0, help="buffer elements (default: the model's)")
     ap.add_argument("--clip", action="store_true",
                     help="also time the gradient-norm pass and the clipped steps")
+    ap.add_argument("--ema", action="store_true",
+                    help="also time the weight-average (EMA) update and its first-update form")
     ap.add_argument("--json", default="")
     a = ap.parse_args(argv)
     if a.iters < 50:
@@ -128,6 +138,33 @@ def main(argv=None):
         fns += [norm, sgd_clip, adam_clip, sumsq]
         rows += [("vae2_grad_sumsq+vae2_clip_coeffs", 4), ("vae2_sgd_step_dev_clip", 20),
                  ("vae2_adam_step_dev_clip", 28), ("vae2_grad_sumsq", 4)]
+    if a.ema:
+        ema = torch.empty(n, device=dev)
+        estate = torch.zeros(2, dtype=torch.float64, device=dev)  # {updates, -}
+        ecoeffs = torch.zeros(4, device=dev)
+        decay = 0.999
+
+        def ema_update():
+            call("vae2_ema_update_dev", ptr(ema), ptr(p), n, ptr(ecoeffs), s)
+
+        def ema_pair():
+            call("vae2_ema_coeffs", ptr(estate), decay, ptr(ecoeffs), s)
+            ema_update()
+
+        def ema_first():
+            call("vae2_ema_update", ptr(ema), ptr(p), n, decay, 1, s)
+
+        # the first update (a copy) runs here, outside the timed window; the second
+        # vae2_ema_coeffs call makes every later device-form launch a steady-state update
+        ema_pair()
+        call("vae2_ema_coeffs", ptr(estate), decay, ptr(ecoeffs), s)
+        if float(estate[0]) != 2.0 or float(ecoeffs[1]) != 0.0:
+            raise RuntimeError("the timed EMA launches would take the first-update path "
+                               f"(count {float(estate[0])}, first flag {float(ecoeffs[1])})")
+        ema_rows = [("vae2_ema_coeffs+vae2_ema_update_dev", 12), ("vae2_ema_update_dev", 12),
+                    ("vae2_ema_update(first)", 8)]
+        fns += [ema_pair, ema_update, ema_first]
+        rows += ema_rows
     times = time_launches(fns, a.iters, a.warmup)
     out = {"numel": n, "iters": a.iters, "sgd_first_step_flag": float(coeffs[2]),
            "sgd_step_counter": float(state[0])}
@@ -135,16 +172,17 @@ def main(argv=None):
         med = statistics.median(ts)
         out[name] = {"median_us": med, "min_us": min(ts), "max_us": max(ts),
                      "bytes": bpe * n, "GBps": bpe * n / med / 1e3}
-        print(f"  {name:20s} median {med:8.1f} us  (min {min(ts):.1f}, max {max(ts):.1f})  "
+        print(f"  {name:36s} median {med:8.1f} us  (min {min(ts):.1f}, max {max(ts):.1f})  "
               f"{bpe} B/elem  {bpe * n / med / 1e3:8.1f} GB/s")
     ratio = out["vae2_sgd_step_dev"]["median_us"] / out["vae2_adam_step_dev"]["median_us"]
     print(f"  sgd / adam median time: {ratio:.3f}")
+    med = {name: out[name]["median_us"] for name, _ in rows}
+    ratios = {}
     if a.clip:
         if float(clip[1]) != 1.0:
             raise RuntimeError(f"the clip coefficient is {float(clip[1])}, not 1")
-        med = {name: out[name]["median_us"] for name, _ in rows}
         out["grad_norm"] = float(clip[0])
-        out["ratios"] = {
+        ratios.update({
             "norm_pass / sgd": {"measured": med[rows[2][0]] / med["vae2_sgd_step_dev"],
                                 "predicted": 4 / 20,
                                 "basis": "4 of SGD's 20 B per element at SGD's rate, plus one "
@@ -155,8 +193,26 @@ def main(argv=None):
             "adam_clip / adam": {"measured": med["vae2_adam_step_dev_clip"]
                                  / med["vae2_adam_step_dev"], "predicted": 1.0,
                                  "basis": "the same bytes, one more multiply per element"},
-        }
-        for k, r in out["ratios"].items():
+        })
+    if a.ema:
+        if float(ecoeffs[1]) != 0.0:
+            raise RuntimeError("a timed EMA launch took the first-update path")
+        out["ema_update_counter"] = float(estate[0])
+        pair, first = med[ema_rows[0][0]], med[ema_rows[2][0]]
+        ratios.update({
+            "ema / adam": {"measured": pair / med["vae2_adam_step_dev"], "predicted": 12 / 28,
+                           "basis": "12 of Adam's 28 B per element at Adam's rate, plus one "
+                                    "small launch"},
+            "ema / sgd": {"measured": pair / med["vae2_sgd_step_dev"], "predicted": 12 / 20,
+                          "basis": "12 of SGD's 20 B per element at SGD's rate, plus one small "
+                                   "launch"},
+            "ema_first / adam": {"measured": first / med["vae2_adam_step_dev"],
+                                 "predicted": 8 / 28,
+                                 "basis": "a copy: 8 of Adam's 28 B per element at Adam's rate"},
+        })
+    if ratios:
+        out["ratios"] = ratios
+        for k, r in ratios.items():
             print(f"  {k:18s} measured {r['measured']:.3f}  predicted {r['predicted']:.3f}")
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)

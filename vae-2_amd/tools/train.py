@@ -17,6 +17,12 @@ train.py:322); epochs past END_EPOCH use the main loader when no
 DATASET.EXTRA_TRAIN_SET is given (the reference raises a NameError there);
 `MI355X.CLIP_GRAD_NORM t` (t > 0) clips the global gradient 2-norm of each optimizer's
 parameter set to t inside the fused step (0, the default, is off);
+`MI355X.EMA_DECAY d` (0 < d < 1; 0, the default, is off) keeps an exponential moving
+average of the generator weights (encz + ED; never the discriminators) on the device,
+updated inside the fused step (vae2.optim, ema_decay): checkpoint_encdec.pth.tar then also
+holds "ema_state_dict" (the averaged parameters with the live BatchNorm buffers) and
+"ema_updates", and the last epoch writes model_encdec_final_state_ema.pth;
+tools/inference.py evaluates the average with MI355X.EVAL_EMA True;
 `MI355X.ELBO_ONLY True` drops the two discriminators (the ELBO step alone; the
 reference always builds them and runs the D step); the Cityscapes sequence zips are
 decoded once into a uint8 cache and normalised on the GPU (MI355X.CLIP_CACHE, default),
@@ -124,6 +130,9 @@ def main(argv=None):
     if not config.MI355X.CLIP_GRAD_NORM >= 0:
         raise ValueError("MI355X.CLIP_GRAD_NORM must be >= 0 (0 = off), got {}".format(
             config.MI355X.CLIP_GRAD_NORM))
+    if not 0 <= config.MI355X.EMA_DECAY < 1:
+        raise ValueError("MI355X.EMA_DECAY must be in [0, 1) (0 = off), got {}".format(
+            config.MI355X.EMA_DECAY))
     extra = config.MODEL.EXTRA
 
     # models, in the reference's construction order (train.py:79-82)
@@ -175,15 +184,17 @@ def main(argv=None):
     nets = [m for m in (encz_model, encdec_model) if m is not None]
     # each parameter set is clipped to the threshold on its own, as two clip_grad_norm_ calls
     clip = float(config.MI355X.CLIP_GRAD_NORM) or None
+    # the weight average is the generator's alone
+    ema_decay = float(config.MI355X.EMA_DECAY) or None
     if config.TRAIN.OPTIMIZER == "sgd":
-        def make_opt(mods):
+        def make_opt(mods, ema_decay=None):
             return FusedSGD(mods, lr=config.TRAIN.LR, momentum=config.TRAIN.MOMENTUM,
                             weight_decay=config.TRAIN.WD, nesterov=config.TRAIN.NESTEROV,
-                            max_grad_norm=clip)
+                            max_grad_norm=clip, ema_decay=ema_decay)
     else:
-        def make_opt(mods):
-            return FusedAdam(mods, lr=config.TRAIN.LR, max_grad_norm=clip)
-    optimizer = make_opt(nets)
+        def make_opt(mods, ema_decay=None):
+            return FusedAdam(mods, lr=config.TRAIN.LR, max_grad_norm=clip, ema_decay=ema_decay)
+    optimizer = make_opt(nets, ema_decay)
     optimizer_D = make_opt([D_model_sequence, D_model_frame]) if use_d else None
     if vdist.is_dist():  # replicas start identical (DDP's initial broadcast)
         for opt in (optimizer, optimizer_D):
@@ -198,6 +209,18 @@ def main(argv=None):
         if os.path.isfile(state_file):
             ck = torch.load(state_file, map_location="cpu", weights_only=True)
             last_epoch = ck["epoch"]
+            if ema_decay is not None and ck.get("ema_updates", 0) > 0 and "ema_state_dict" in ck:
+                # seed the average from the live parameters so that swap_ema() is legal, then
+                # load the saved average into the parameters' place inside it
+                with torch.no_grad():
+                    for f, e in zip(optimizer.flats, optimizer.ema):
+                        e.copy_(f.data)
+                    optimizer.ema_updates = int(ck["ema_updates"])
+                with optimizer.swap_ema():
+                    model_encdec.load_state_dict(ck["ema_state_dict"], strict=use_d)
+            elif ema_decay is not None:
+                logger.info("=> the checkpoint holds no EMA weights: the average starts from "
+                            "the first update of this run")
             model_encdec.load_state_dict(ck["state_dict"], strict=use_d)
             optimizer.load_state_dict(ck["optimizer_encdec"])
             logger.info("=> loaded checkpoint (epoch {})".format(ck["epoch"]))
@@ -232,8 +255,14 @@ def main(argv=None):
                           is_baseline=extra.IS_BASELINE, baseline_mode=extra.BASELINE_MODE)
         if vdist.rank() == 0:  # train.py:317-348
             logger.info("=> saving checkpoint to {}".format(state_file))
-            torch.save({"epoch": epoch + 1, "state_dict": model_encdec.state_dict(),
-                        "optimizer_encdec": optimizer.state_dict()}, state_file)
+            ck = {"epoch": epoch + 1, "state_dict": model_encdec.state_dict(),
+                  "optimizer_encdec": optimizer.state_dict()}
+            if ema_decay is not None:
+                with optimizer.swap_ema():
+                    ck["ema_state_dict"] = {k: v.clone()
+                                            for k, v in model_encdec.state_dict().items()}
+                ck["ema_updates"] = optimizer.ema_updates
+            torch.save(ck, state_file)
             if use_d:
                 logger.info("=> saving checkpoint to {}".format(state_file_D))
                 torch.save({"epoch": epoch + 1, "state_dict": model_D.state_dict(),
@@ -241,6 +270,10 @@ def main(argv=None):
             if epoch == end_epoch - 1:
                 torch.save(model_encdec.state_dict(),
                            os.path.join(final_output_dir, "model_encdec_final_state.pth"))
+                if ema_decay is not None:
+                    torch.save(ck["ema_state_dict"],
+                               os.path.join(final_output_dir,
+                                            "model_encdec_final_state_ema.pth"))
                 if use_d:
                     torch.save(model_D.state_dict(),
                                os.path.join(final_output_dir, "model_D_final_state.pth"))

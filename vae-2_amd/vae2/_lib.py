@@ -167,6 +167,9 @@ _SIGS = {
     "vae2_adam_step_dev_clip": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_f32, c_f32,
                                         c_f32, c_f32, c_vp]),
     "vae2_scale_dev": (c_int, [c_vp, c_i64, c_vp, c_vp]),
+    "vae2_ema_coeffs": (c_int, [c_vp, c_f32, c_vp, c_vp]),
+    "vae2_ema_update_dev": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "vae2_ema_update": (c_int, [c_vp, c_vp, c_i64, c_f32, c_int, c_vp]),
     "vae2_scale": (c_int, [c_vp, c_vp, c_i64, c_f32, c_vp]),
     "vae2_syncbn_comm_bytes": (c_i64, [c_int, c_i64]),
     "vae2_syncbn_comm_init": (c_int, [c_int, c_int, c_i64, c_vp, ctypes.POINTER(c_vp)]),
@@ -193,7 +196,7 @@ _SIGS = {
     "vae2_conv2d_set_grouping": (c_int, [c_int]),
 }
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 _lib = None
 
 

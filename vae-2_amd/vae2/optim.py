@@ -20,7 +20,20 @@ on the device by every step, so a captured step replays them; grad_norm() return
 device value of the last step without synchronising.  In the distributed loop
 allreduce_grads runs before step(), so the norm is that of the reduced gradient and is
 identical on every rank.  clip_grad_norm_ below is the stand-alone, torch-shaped form.
+
+ema_decay (both optimizers; None = off: no buffers, and the launches are exactly those
+without it) keeps an exponential moving average of the weights in `ema`, one buffer per flat
+parameter buffer, with the semantics of torch.optim.swa_utils.AveragedModel +
+get_ema_multi_avg_fn(decay): the first update copies the weights, later ones do
+ema += (1 - decay) * (p - ema).  step() launches one vae2_ema_coeffs and one
+vae2_ema_update_dev per flat buffer after the parameter update; the update count lives on
+the device (ema_updates), so "first update" is decided there and a captured step replays it.
+swap_ema() exchanges the contents of the weights and their average (and re-packs the conv
+weights) for evaluation.  BatchNorm running statistics are buffers, not parameters: they are
+not averaged, and under swap_ema() the model runs with the live ones.  ema_decay is
+configuration, not optimizer state: param_groups and state_dict() do not carry it.
 """
+import contextlib
 import math
 
 import torch
@@ -37,6 +50,16 @@ def _clip_threshold(max_norm, what="max_grad_norm"):
     v = float(max_norm)
     if math.isnan(v) or v <= 0.0:
         raise ValueError(f"Invalid {what}: {max_norm} (None, or a float > 0)")
+    return v
+
+
+def _ema_decay(decay):
+    """None (off) or a float in [0, 1), else ValueError."""
+    if decay is None:
+        return None
+    v = float(decay)
+    if not 0.0 <= v < 1.0:  # NaN fails both comparisons
+        raise ValueError(f"Invalid ema_decay: {decay} (None, or a float in [0, 1))")
     return v
 
 
@@ -64,8 +87,9 @@ class _FusedFlat:
     """What the fused optimizers share: the flat buffers and weight packs of their modules,
     the device-resident {step, lr} state, learning-rate sync and zero_grad."""
 
-    def _init_flat(self, modules, lr, n_coeffs, max_grad_norm=None):
+    def _init_flat(self, modules, lr, n_coeffs, max_grad_norm=None, ema_decay=None):
         self.max_grad_norm = _clip_threshold(max_grad_norm)
+        self.ema_decay = _ema_decay(ema_decay)
         if not isinstance(modules, (list, tuple)):
             modules = [modules]
         self.flats = [flatten(m) for m in modules]
@@ -78,6 +102,68 @@ class _FusedFlat:
         self._dev_lr = None
         # allocated here, never in step(): the step may be the one a graph captures
         self._norm = _GradNorm(self.flats) if self.max_grad_norm is not None else None
+        self.ema = None
+        if self.ema_decay is not None:
+            # not read before the first update (the kernel copies then), so left uninitialised
+            self.ema = [torch.empty_like(f.data) for f in self.flats]
+            self._ema_state = torch.zeros(2, dtype=torch.float64, device=dev)  # {updates, -}
+            self._ema_coeffs = torch.zeros(4, dtype=torch.float32, device=dev)
+
+    def _finish_step(self, s):
+        """After the parameter update of all flats: the EMA update, then the re-pack."""
+        if self.ema is not None:
+            call("vae2_ema_coeffs", ops.ptr(self._ema_state), self.ema_decay,
+                 ops.ptr(self._ema_coeffs), s)
+            for f, e in zip(self.flats, self.ema):
+                call("vae2_ema_update_dev", ops.ptr(e), ops.ptr(f.data), f.numel,
+                     ops.ptr(self._ema_coeffs), s)
+        for plan in self.packs:
+            plan.bump_versions()
+
+    @property
+    def ema_updates(self):
+        """The number of EMA updates so far (the device counter: one synchronising read)."""
+        if self.ema is None:
+            return 0
+        return int(self._ema_state[0].item())
+
+    @ema_updates.setter
+    def ema_updates(self, n):
+        if self.ema is None:
+            raise RuntimeError("ema_updates: the optimizer was built with ema_decay=None")
+        self._ema_state[0].fill_(float(n))
+
+    def _exchange_ema(self):
+        for f, e in zip(self.flats, self.ema):
+            tmp = f.data.clone()
+            f.data.copy_(e)
+            e.copy_(tmp)
+        for plan in self.packs:
+            plan.bump_versions()
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """Run the model with the averaged weights: the contents of each flat parameter buffer
+        and its `ema` buffer are exchanged (parameter views and pointers keep their identity)
+        and the conv weights re-packed; on exit, also on an exception, they are exchanged
+        back.  BatchNorm running statistics stay the live ones.  An epoch-boundary operation
+        (plain copies, one synchronising read), not for use inside a captured step."""
+        if self.ema is None:
+            raise RuntimeError("swap_ema(): the optimizer was built with ema_decay=None")
+        if self.flats[0].data.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("swap_ema(): not inside a graph capture")
+        streams.join_all()
+        if self.ema_updates == 0:
+            raise RuntimeError("swap_ema(): no EMA update has happened yet (ema_updates == 0: "
+                               "the ema buffers are uninitialised)")
+        with torch.no_grad():
+            self._exchange_ema()
+        try:
+            yield self
+        finally:
+            streams.join_all()
+            with torch.no_grad():
+                self._exchange_ema()
 
     def grad_norm(self):
         """The total gradient 2-norm of the last step(): a 0-dim device tensor (a view of
@@ -139,8 +225,8 @@ def _check_kind(st, want, other, name):
 
 class FusedAdam(_FusedFlat):
     def __init__(self, modules, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 max_grad_norm=None):
-        self._init_flat(modules, lr, 2, max_grad_norm)
+                 max_grad_norm=None, ema_decay=None):
+        self._init_flat(modules, lr, 2, max_grad_norm, ema_decay)
         self.betas = (float(betas[0]), float(betas[1]))
         self.eps = float(eps)
         self.weight_decay = float(weight_decay)
@@ -170,8 +256,7 @@ class FusedAdam(_FusedFlat):
                 call("vae2_adam_step_dev", ops.ptr(f.data), ops.ptr(f.grad), ops.ptr(m),
                      ops.ptr(v), f.numel, ops.ptr(self._coeffs), self.betas[0], self.betas[1],
                      self.eps, self.weight_decay, s)
-        for plan in self.packs:
-            plan.bump_versions()
+        self._finish_step(s)
 
     # ---- torch.optim.Adam-compatible checkpoint format ----
     def state_dict(self):
@@ -215,7 +300,7 @@ class FusedSGD(_FusedFlat):
     gradient) is refused with a ValueError."""
 
     def __init__(self, modules, lr, momentum=0.0, dampening=0.0, weight_decay=0.0,
-                 nesterov=False, max_grad_norm=None):
+                 nesterov=False, max_grad_norm=None, ema_decay=None):
         # torch.optim.SGD's own checks and messages, before any buffer is built
         if lr < 0.0:
             raise ValueError(f"Invalid learning rate: {lr}")
@@ -225,7 +310,7 @@ class FusedSGD(_FusedFlat):
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        self._init_flat(modules, lr, 4, max_grad_norm)
+        self._init_flat(modules, lr, 4, max_grad_norm, ema_decay)
         self.momentum = float(momentum)
         self.dampening = float(dampening)
         self.weight_decay = float(weight_decay)
@@ -269,8 +354,7 @@ class FusedSGD(_FusedFlat):
                 call("vae2_sgd_step_dev", ops.ptr(f.data), ops.ptr(f.grad),
                      ops.ptr(b) if b is not None else None, f.numel, ops.ptr(self._coeffs),
                      self.momentum, self.weight_decay, int(self.nesterov), s)
-        for plan in self.packs:
-            plan.bump_versions()
+        self._finish_step(s)
 
     # ---- torch.optim.SGD-compatible checkpoint format ----
     def state_dict(self):
