@@ -12,6 +12,12 @@
  *   - Activations are NHWC fp32 views described by vae2_act:
  *        element (n, y, x, c) lives at ptr[((n*h + y)*w + x)*ps + c],  ps >= c.
  *     A channel slice of a wider buffer is (ptr + c0, ps = width of the buffer).
+ *   - The element-wise activation kernels count n*h*w*c in 32 bits: an activation of
+ *     2^31 or more elements is rejected with -22 ("tensor too large") by the loss
+ *     (l1, lsgan, reparam_kl), ReLU-backward, copy, code-map tile, layout-conversion,
+ *     average-pool-backward, upsample and fuse-sum entry points.  Operands of one call
+ *     must agree in shape (n, h, w and, where they hold the same quantity, c); a
+ *     mismatch is rejected with -22 as well, never read or written out of bounds.
  *   - Conv weights keep the reference's nn.Conv2d layout [Cout][Cin][KH][KW]
  *     (so state_dicts interchange); conv biases are [Cout].
  *   - `stream` is a hipStream_t (PyTorch: torch.cuda.current_stream().cuda_stream).

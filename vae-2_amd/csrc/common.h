@@ -144,6 +144,17 @@ inline bool act_ok(const vae2_act* d) {
 inline int64_t act_pixels(const vae2_act* d) { return d->n * d->h * d->w; }
 inline int64_t act_elems(const vae2_act* d) { return d->n * d->h * d->w * d->c; }
 
+// Kernels that count elements in uint32_t and decode them with FastDiv::div take fewer than
+// 2^31 of them: from n = 2^31 on FastDiv's __umulhi(n, m) + n can overflow (m < 2^32).
+constexpr const char* kTooLarge = "tensor too large: 2^31 or more elements (32-bit indexing)";
+inline bool idx32_ok(const vae2_act* d) { return act_elems(d) < (int64_t(1) << 31); }
+inline bool same_shape(const vae2_act* a, const vae2_act* b) {
+  return a->n == b->n && a->h == b->h && a->w == b->w && a->c == b->c;
+}
+inline bool same_nhw(const vae2_act* a, const vae2_act* b) {
+  return a->n == b->n && a->h == b->h && a->w == b->w;
+}
+
 constexpr int kWave = 64;
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -539,6 +539,7 @@ int vae2_l1_fwd(const float* p, const vae2_act* pd, const float* t,
   VAE2_REQUIRE(p && t && ws && out && act_ok(pd) && act_ok(td), fn, "bad arguments");
   VAE2_REQUIRE(pd->n == td->n && pd->h == td->h && pd->w == td->w && pd->c == td->c, fn,
                "predict / target shape mismatch");
+  VAE2_REQUIRE(idx32_ok(pd), fn, kTooLarge);
   int64_t total = act_elems(pd);
   unsigned nb = reduce_blocks(total);
   hipStream_t s = as_stream(stream);
@@ -557,6 +558,9 @@ int vae2_l1_bwd(const float* p, const vae2_act* pd, const float* t,
   const char* fn = "vae2_l1_bwd";
   VAE2_REQUIRE(p && t && gout && dp && act_ok(pd) && act_ok(td) && act_ok(dpd), fn,
                "bad arguments");
+  VAE2_REQUIRE(same_shape(td, pd), fn, "predict / target shape mismatch");
+  VAE2_REQUIRE(same_shape(dpd, pd), fn, "dp shape mismatch");
+  VAE2_REQUIRE(idx32_ok(pd), fn, kTooLarge);
   int64_t total = act_elems(pd);
   VAE2_LAUNCH(l1_bwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream), p,
                      to_act(pd), t, to_act(td), gout, scale, dp, to_act(dpd), beta,
@@ -568,6 +572,7 @@ int vae2_lsgan_fwd(const float* x, const vae2_act* xd, float target, float scale
                    float* out, void* stream) {
   const char* fn = "vae2_lsgan_fwd";
   VAE2_REQUIRE(x && ws && out && act_ok(xd), fn, "bad arguments");
+  VAE2_REQUIRE(idx32_ok(xd), fn, kTooLarge);
   const int64_t total = act_elems(xd);
   const unsigned nb = reduce_blocks(total);
   hipStream_t s = as_stream(stream);
@@ -586,6 +591,7 @@ int vae2_lsgan_bwd(const float* x, const vae2_act* xd, float target, const float
   VAE2_REQUIRE(x && gout && dx && act_ok(xd) && act_ok(dxd), fn, "bad arguments");
   VAE2_REQUIRE(dxd->n == xd->n && dxd->h == xd->h && dxd->w == xd->w && dxd->c == xd->c, fn,
                "dx shape mismatch");
+  VAE2_REQUIRE(idx32_ok(xd), fn, kTooLarge);
   const int64_t total = act_elems(xd);
   VAE2_LAUNCH(sqdiff_bwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
                      x, to_act(xd), target, gout, scale, dx, to_act(dxd), beta,
@@ -601,6 +607,8 @@ int vae2_reparam_kl_fwd(const float* muvar, const vae2_act* md,
   VAE2_REQUIRE(muvar && eps && z && kl_out && ws && act_ok(md) && act_ok(ed) && act_ok(zd), fn,
                "bad arguments");
   VAE2_REQUIRE(md->c == 2 * zd->c && ed->c == zd->c, fn, "channel mismatch");
+  VAE2_REQUIRE(same_nhw(md, zd) && same_nhw(ed, zd), fn, "muvar / eps / z n, h, w mismatch");
+  VAE2_REQUIRE(idx32_ok(zd), fn, kTooLarge);
   int64_t total = act_elems(zd);
   unsigned nb = reduce_blocks(total);
   hipStream_t s = as_stream(stream);
@@ -621,6 +629,11 @@ int vae2_reparam_kl_bwd(const float* muvar, const vae2_act* md,
   VAE2_REQUIRE(muvar && eps && dmuvar && act_ok(md) && act_ok(ed) && act_ok(dmd), fn,
                "bad arguments");
   VAE2_REQUIRE(!dz || act_ok(dzd), fn, "bad dz descriptor");
+  VAE2_REQUIRE(md->c == 2 * ed->c, fn, "channel mismatch");
+  VAE2_REQUIRE(same_nhw(md, ed), fn, "muvar / eps n, h, w mismatch");
+  VAE2_REQUIRE(same_shape(dmd, md), fn, "dmuvar shape mismatch");
+  VAE2_REQUIRE(!dz || same_shape(dzd, ed), fn, "dz shape mismatch");
+  VAE2_REQUIRE(idx32_ok(ed), fn, kTooLarge);
   int64_t total = act_elems(ed);
   Act dza = dz ? to_act(dzd) : to_act(ed);
   VAE2_LAUNCH(reparam_kl_bwd_kernel, dim3(ew_blocks(total)), dim3(256), 0,

@@ -909,6 +909,7 @@ int vae2_relu_bwd(const float* dy, const vae2_act* dyd, const float* y,
   VAE2_REQUIRE(dy && y && g && act_ok(dyd) && act_ok(yd) && act_ok(gd), fn, "bad arguments");
   VAE2_REQUIRE(same_hw(dyd, yd) && same_hw(yd, gd) && dyd->c == yd->c && gd->c == yd->c, fn,
                "shape mismatch");
+  VAE2_REQUIRE(idx32_ok(yd), fn, kTooLarge);
   int64_t total = act_elems(yd);
   VAE2_LAUNCH(relu_bwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
                      dy, to_act(dyd), y, to_act(yd), g, to_act(gd), FastDiv((uint32_t)yd->c));
@@ -923,6 +924,7 @@ int vae2_relu_bwd_dual(const float* dy, const vae2_act* dyd, const float* y,
                fn, "bad arguments");
   VAE2_REQUIRE(same_hw(dyd, yd) && same_hw(yd, gd) && same_hw(yd, g2d) && dyd->c == yd->c &&
                    gd->c == yd->c && g2d->c == yd->c, fn, "shape mismatch");
+  VAE2_REQUIRE(idx32_ok(yd), fn, kTooLarge);
   int64_t total = act_elems(yd);
   auto q16 = [](const float* ptr, const vae2_act* d) {
     return ((uintptr_t)ptr % 16 == 0) && d->ps % 4 == 0;
@@ -945,6 +947,7 @@ int vae2_copy_act(const float* x, const vae2_act* xd, float* y,
   const char* fn = "vae2_copy_act";
   VAE2_REQUIRE(x && y && act_ok(xd) && act_ok(yd), fn, "bad arguments");
   VAE2_REQUIRE(same_hw(xd, yd) && xd->c == yd->c, fn, "shape mismatch");
+  VAE2_REQUIRE(idx32_ok(xd), fn, kTooLarge);
   int64_t total = act_elems(xd);
   VAE2_LAUNCH(copy_act_kernel, dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
                      x, to_act(xd), y, to_act(yd), beta, FastDiv((uint32_t)xd->c));
@@ -955,6 +958,7 @@ int vae2_codemap_tile_fwd(const float* v, int64_t vs, float* y,
                           const vae2_act* yd, void* stream) {
   const char* fn = "vae2_codemap_tile_fwd";
   VAE2_REQUIRE(v && y && act_ok(yd) && vs >= yd->c, fn, "bad arguments");
+  VAE2_REQUIRE(idx32_ok(yd), fn, kTooLarge);
   int64_t total = act_elems(yd);
   VAE2_LAUNCH(tile_kernel, dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream), v,
                      vs, y, to_act(yd), 1.f, 0.f, FastDiv((uint32_t)yd->c),
@@ -979,6 +983,7 @@ int vae2_nchw_to_nhwc(const float* x, float* y, const vae2_act* yd,
                       float beta, void* stream) {
   const char* fn = "vae2_nchw_to_nhwc";
   VAE2_REQUIRE(x && y && act_ok(yd), fn, "bad arguments");
+  VAE2_REQUIRE(idx32_ok(yd), fn, kTooLarge);
   int64_t total = act_elems(yd);
   VAE2_LAUNCH(nchw_to_nhwc_kernel, dim3(ew_blocks(total)), dim3(256), 0,
                      as_stream(stream), x, y, to_act(yd), beta, FastDiv((uint32_t)yd->c),
@@ -990,6 +995,7 @@ int vae2_nhwc_to_nchw(const float* x, const vae2_act* xd, float* y,
                       float beta, void* stream) {
   const char* fn = "vae2_nhwc_to_nchw";
   VAE2_REQUIRE(x && y && act_ok(xd), fn, "bad arguments");
+  VAE2_REQUIRE(idx32_ok(xd), fn, kTooLarge);
   int64_t total = act_elems(xd);
   VAE2_LAUNCH(nhwc_to_nchw_kernel, dim3(ew_blocks(total)), dim3(256), 0,
                      as_stream(stream), x, to_act(xd), y, beta, FastDiv((uint32_t)xd->c),
@@ -1025,6 +1031,7 @@ int vae2_weighted_avgpool_bwd(const float* dy, const vae2_act* dyd, const float*
   VAE2_REQUIRE(dy && dx && wr && wc && act_ok(dyd) && act_ok(dxd), fn, "bad arguments");
   VAE2_REQUIRE(dyd->h == 1 && dyd->w == 1 && dyd->n == dxd->n && dyd->c == dxd->c, fn,
                "dy must be (n, 1, 1, c)");
+  VAE2_REQUIRE(idx32_ok(dxd), fn, kTooLarge);
   int64_t total = act_elems(dxd);
   VAE2_LAUNCH(tile_kernel, dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream), dy,
               dyd->ps, dx, to_act(dxd), scale, beta, FastDiv((uint32_t)dxd->c),
@@ -1038,6 +1045,7 @@ int vae2_global_avgpool_bwd(const float* dy, const vae2_act* dyd, float* dx,
   VAE2_REQUIRE(dy && dx && act_ok(dyd) && act_ok(dxd), fn, "bad arguments");
   VAE2_REQUIRE(dyd->h == 1 && dyd->w == 1 && dyd->n == dxd->n && dyd->c == dxd->c, fn,
                "dy must be (n, 1, 1, c)");
+  VAE2_REQUIRE(idx32_ok(dxd), fn, kTooLarge);
   int64_t total = act_elems(dxd);
   VAE2_LAUNCH(tile_kernel, dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream), dy,
                      dyd->ps, dx, to_act(dxd), 1.f / (float)(dxd->h * dxd->w), beta,
