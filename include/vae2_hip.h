@@ -571,6 +571,37 @@ int vae2_lsgan_fwd(const float* x, const vae2_act* xd, float target, float scale
 int vae2_lsgan_bwd(const float* x, const vae2_act* xd, float target, const float* gout,
                    float scale, float* dx, const vae2_act* dxd, float beta, void* stream);
 
+/* SSIM reconstruction term (MI355X.SSIM_LAMBDA; not in the reference).  p, t: NHWC views
+ * of the same n, h, w, c (any ps >= c), h, w >= 11.  a, b: per-channel device coefficients
+ * [c], both NULL meaning a = 1, b = 0.  g: the 11-tap fp32 Gaussian window (sigma 1.5,
+ * normalised) of vae2/metrics.py::_win, applied separably as a valid filter G = g x g:
+ *   u = a_c p + b_c,  v = a_c t + b_c                                  (per channel c)
+ *   mu1 = G*u, mu2 = G*v, e11 = G*u^2, e22 = G*v^2, e12 = G*uv    ((h-10) x (w-10) maps)
+ *   s1 = e11 - mu1^2, s2 = e22 - mu2^2, s12 = e12 - mu1 mu2
+ *   A1 = 2 mu1 mu2 + c1, B1 = mu1^2 + mu2^2 + c1, A2 = 2 s12 + c2, B2 = s1 + s2 + c2
+ *   ssim = (A1 / B1) (A2 / B2)
+ *   out[0] = scale * sum_{n,c} sum_{valid pixels} (1 - ssim)
+ * (oracle/metrics_ref.py::_ssim's ssim_map, summed).  fp32 maps, fp64 per-workgroup
+ * partials in ws (vae2_ssim_loss_ws_size(pd) doubles, >= 1) summed in a fixed order: two
+ * runs give the same bits; p == t gives exactly 0.
+ * Backward, p only; with l = A1 / B1, cs = A2 / B2 and on the valid domain
+ *   D11 = -l cs / B2                                   (d ssim / d e11)
+ *   D12 = 2 l / B2                                     (d ssim / d e12)
+ *   Dmu = cs 2 (mu2 - mu1 l) / B1 - 2 mu1 D11 - mu2 D12  (d ssim / d mu1, total)
+ *   dp (+)= -scale gout[0] a_c [ Gt*Dmu + 2 u (Gt*D11) + v (Gt*D12) ]
+ * Gt*: the transposed (full) separable correlation back onto h x w; gout a device scalar;
+ * beta 0: overwrite, 1: accumulate.  The maps are recomputed from p, t (no saved state,
+ * no workspace, no atomics).
+ * Limits (-22 otherwise): fewer than 2^31 elements; c1, c2 finite and > 0; a workgroup
+ * takes 3 channels of one image, so n * ceil(c / 3) <= 65535 and ceil(h / 16) <= 65535. */
+int64_t vae2_ssim_loss_ws_size(const vae2_act* pd);
+int vae2_ssim_loss_fwd(const float* p, const vae2_act* pd, const float* t, const vae2_act* td,
+                       const float* a, const float* b, float c1, float c2, float scale,
+                       double* ws, float* out, void* stream);
+int vae2_ssim_loss_bwd(const float* p, const vae2_act* pd, const float* t, const vae2_act* td,
+                       const float* a, const float* b, float c1, float c2, const float* gout,
+                       float scale, float* dp, const vae2_act* dpd, float beta, void* stream);
+
 /* Reparameterisation + KL (utils.py:85-101, criterion.py:72-87).
  * muvar: act with 2*zc channels (mu = [0,zc), logvar = [zc,2zc)); eps, z: acts
  * with zc channels.  prior != 0: z = eps (prior_sampling).

@@ -60,6 +60,10 @@ _SCHEMA = {
         # by the fused step (FusedAdam / FusedSGD ema_decay), in [0, 1); 0 = off
         "EMA_DECAY": 0.0,
         "EVAL_EMA": False,        # tools/inference.py: evaluate the checkpoint's averaged weights
+        # weight of the SSIM sibling of every L1 reconstruction term: each gains
+        # SSIM_LAMBDA * X?RECON_LAMBDA * sum (1 - SSIM) / batch (vae2.ops.ssim_loss); >= 0,
+        # 0 = off (the reference's L1 + KL (+ LSGAN))
+        "SSIM_LAMBDA": 0.0,
     },
 }
 

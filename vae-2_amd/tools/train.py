@@ -23,6 +23,10 @@ updated inside the fused step (vae2.optim, ema_decay): checkpoint_encdec.pth.tar
 holds "ema_state_dict" (the averaged parameters with the live BatchNorm buffers) and
 "ema_updates", and the last epoch writes model_encdec_final_state_ema.pth;
 tools/inference.py evaluates the average with MI355X.EVAL_EMA True;
+`MI355X.SSIM_LAMBDA s` (s > 0; 0, the default, is off) gives every L1 reconstruction term
+an SSIM sibling, sum (1 - SSIM) / batch of the de-normalised frames with the weight
+s * X?RECON_LAMBDA (vae2.ops.ssim_loss: the evaluation's SSIM without its clip to
+[0, 255]), logged as loss_x?t_ssim next to the PRINT_FREQ line;
 `MI355X.ELBO_ONLY True` drops the two discriminators (the ELBO step alone; the
 reference always builds them and runs the D step); the Cityscapes sequence zips are
 decoded once into a uint8 cache and normalised on the GPU (MI355X.CLIP_CACHE, default),
@@ -133,6 +137,9 @@ def main(argv=None):
     if not 0 <= config.MI355X.EMA_DECAY < 1:
         raise ValueError("MI355X.EMA_DECAY must be in [0, 1) (0 = off), got {}".format(
             config.MI355X.EMA_DECAY))
+    if not config.MI355X.SSIM_LAMBDA >= 0:
+        raise ValueError("MI355X.SSIM_LAMBDA must be >= 0 (0 = off), got {}".format(
+            config.MI355X.SSIM_LAMBDA))
     extra = config.MODEL.EXTRA
 
     # models, in the reference's construction order (train.py:79-82)
@@ -170,7 +177,7 @@ def main(argv=None):
         D_model_frame=D_model_frame, criterion_recon=L1Loss(), criterion_KL=KLLoss(),
         criterion_gan=lsgan_adversarial_loss(), x1recon_lambda=config.TRAIN.X1RECON_LAMBDA,
         x2recon_lambda=config.TRAIN.X2RECON_LAMBDA, x3recon_lambda=config.TRAIN.X3RECON_LAMBDA,
-        gan_lambda=config.TRAIN.GAN_LAMBDA)
+        gan_lambda=config.TRAIN.GAN_LAMBDA, ssim_lambda=float(config.MI355X.SSIM_LAMBDA))
     model_encdec.defer_checks = config.MI355X.DEFER_CHECKS
     model_encdec = model_encdec.to(device)
     model_D = None

@@ -136,6 +136,11 @@ _SIGS = {
     "vae2_reduce_ws_size": (c_i64, [c_i64]),
     "vae2_l1_fwd": (c_int, [c_vp, P_ACT, c_vp, P_ACT, c_f32, c_vp, c_vp, c_vp]),
     "vae2_l1_bwd": (c_int, [c_vp, P_ACT, c_vp, P_ACT, c_vp, c_f32, c_vp, P_ACT, c_f32, c_vp]),
+    "vae2_ssim_loss_ws_size": (c_i64, [P_ACT]),
+    "vae2_ssim_loss_fwd": (c_int, [c_vp, P_ACT, c_vp, P_ACT, c_vp, c_vp, c_f32, c_f32, c_f32,
+                                   c_vp, c_vp, c_vp]),
+    "vae2_ssim_loss_bwd": (c_int, [c_vp, P_ACT, c_vp, P_ACT, c_vp, c_vp, c_f32, c_f32, c_vp,
+                                   c_f32, c_vp, P_ACT, c_f32, c_vp]),
     "vae2_bn_multi_apply": (c_int, [c_int, c_vp, c_vp]),
     "vae2_bn_multi_bwd_reduce": (c_int, [c_int, c_vp, c_vp]),
     "vae2_bn_multi_bwd_apply": (c_int, [c_int, c_vp, c_vp]),

@@ -17,6 +17,19 @@ class L1Loss(nn.Module):
         return ops.l1(predict, target, 1.0 / predict.shape[0], flat=True)
 
 
+class SSIMLoss(nn.Module):
+    """sum (1 - SSIM(predict, target)) / batch over channels and valid pixels, of the frames
+    de-normalised to [0, 1] (vae2.metrics MEAN / STD, C1 = 0.01^2, C2 = 0.03^2): the
+    evaluation's SSIM without _to_image's clip (ops.ssim_loss).  NCHW in, like L1Loss; the
+    sibling of L1Loss that MI355X.SSIM_LAMBDA adds, not in the reference."""
+
+    def forward(self, predict, target):
+        p = ops.to_nhwc(predict)
+        t = ops.to_nhwc(target)
+        a, b = ops.ssim_coeffs(p.device, p.shape[3])
+        return ops.ssim_loss(p, t, 1.0 / predict.shape[0], a, b)
+
+
 def _muvar_nhwc(m, v):
     # (N, z, h, w) NCHW pair -> (N, h, w, 2z) NHWC
     return ops.to_nhwc(torch.cat([m, v], dim=1))

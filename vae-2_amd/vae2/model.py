@@ -26,6 +26,13 @@ parameters are frozen during the generator pass so no weight gradient is compute
 for them (same results, less work).  With GAN_LAMBDA 0 the terms are evaluated
 without autograd (their gradient is exactly zero).
 
+SSIM terms (not in the reference): with `ssim_lambda` > 0 (MI355X.SSIM_LAMBDA) every L1
+reconstruction term of the mode gains the sibling ops.ssim_loss(x?_hat, x?, 1/B) of the
+frames de-normalised to [0, 1], weighted ssim_lambda * X?RECON_LAMBDA in loss_all.  The
+returned list keeps its seven reference-shaped entries (L1 only in the recon slots); the
+unweighted SSIM terms are on `self.ssim_terms` (a tuple of device scalars, None when off).
+With ssim_lambda == 0 the forward issues exactly the launches it did before.
+
 FullModel_D (utils.py:244-276): the discriminator loss of the D step.
 """
 import contextlib
@@ -41,7 +48,8 @@ _MODES = ("VAE_NATIVE", "VAE_ANNEAL", "VAE_GAN", "DETERMINISTIC")
 class FullModel_encdec(nn.Module):  # noqa: N801 (reference name)
     def __init__(self, encz_model, encdec_model, D_model_sequence, D_model_frame,
                  criterion_recon, criterion_KL, criterion_gan,
-                 x1recon_lambda=1.0, x2recon_lambda=1.0, x3recon_lambda=1.0, gan_lambda=1.0):
+                 x1recon_lambda=1.0, x2recon_lambda=1.0, x3recon_lambda=1.0, gan_lambda=1.0,
+                 ssim_lambda=0.0):
         super().__init__()
         self.encz_model = encz_model
         self.encdec_model = encdec_model
@@ -54,6 +62,10 @@ class FullModel_encdec(nn.Module):  # noqa: N801 (reference name)
         self.x2recon_lambda = x2recon_lambda
         self.x3recon_lambda = x3recon_lambda
         self.gan_lambda = gan_lambda
+        if not ssim_lambda >= 0:
+            raise ValueError("ssim_lambda must be >= 0 (0 = off), got {}".format(ssim_lambda))
+        self.ssim_lambda = float(ssim_lambda)
+        self.ssim_terms = None
         self.defer_checks = False
         self._flag = None
         self._noise = None
@@ -106,6 +118,14 @@ class FullModel_encdec(nn.Module):  # noqa: N801 (reference name)
             frame = ops.weighted_sum(fl, [1.0] * len(fl))
         return seq, frame
 
+    def _ssim_sum(self, pairs, B):
+        """sum_i ssim_lambda * lambda_i * ssim_loss(pred_i, target_i) / B for the
+        (pred, target, lambda) reconstruction pairs of the mode, as one term (the assembly
+        takes at most 8, and the full mode already has 6); keeps the unweighted terms."""
+        a, b = ops.ssim_coeffs(pairs[0][0].device, pairs[0][0].shape[3])
+        self.ssim_terms = tuple(ops.ssim_loss(p, t, 1.0 / B, a, b) for p, t, _ in pairs)
+        return ops.weighted_sum(self.ssim_terms, [self.ssim_lambda * lam for _, _, lam in pairs])
+
     # ---- forward ---------------------------------------------------------------
     def forward(self, xt, x2t, x3t, multiplier, is_baseline=False, baseline_mode="VAE_NATIVE",
                 sampling_mode="default", xt_last=None, x3t_last=None):
@@ -127,6 +147,10 @@ class FullModel_encdec(nn.Module):  # noqa: N801 (reference name)
         x2t_n = ops.to_nhwc(x2t)
         x3t_n = ops.to_nhwc(x3t)
         H, W = xt_n.shape[1:3]
+        self.ssim_terms = None
+        if self.ssim_lambda > 0 and min(H, W) < 11:
+            raise ValueError("MI355X.SSIM_LAMBDA > 0 needs frames of at least 11 x 11 (the SSIM "
+                             "window), got {} x {}".format(H, W))
 
         enc_in = ops.cat([xt_n, x2t_n], (H, W)) if is_baseline else xt_n
         z = None
@@ -177,6 +201,8 @@ class FullModel_encdec(nn.Module):  # noqa: N801 (reference name)
             gan_seq, gan_frame = self._gan_terms(x2p, x2t.shape[1] // ed.clip_length)
             terms = [xt_recon, x2t_recon, x3t_recon, z_kl]
             lams = [self.x1recon_lambda, self.x2recon_lambda, self.x3recon_lambda, kl_lambda]
+            recon_pairs = [(x1p, xt_n, self.x1recon_lambda), (x2p, x2t_n, self.x2recon_lambda),
+                           (x3p, x3t_n, self.x3recon_lambda)]
             if torch.is_tensor(gan_seq) and self.gan_lambda != 0:
                 terms += [gan_seq, gan_frame]
                 lams += [self.gan_lambda, self.gan_lambda]
@@ -185,6 +211,7 @@ class FullModel_encdec(nn.Module):  # noqa: N801 (reference name)
             x3t_recon = 0.0
             x2t_recon = ops.l1(x2p, x3t_n, scale)
             terms, lams = [x2t_recon], [self.x2recon_lambda]
+            recon_pairs = [(x2p, x3t_n, self.x2recon_lambda)]
             gan_seq, gan_frame = 0.0, 0.0
             if baseline_mode in ("VAE_NATIVE", "VAE_ANNEAL"):
                 z_kl = kl
@@ -200,6 +227,9 @@ class FullModel_encdec(nn.Module):  # noqa: N801 (reference name)
                 if torch.is_tensor(gan_seq) and self.gan_lambda != 0:
                     terms += [gan_seq, gan_frame]
                     lams += [self.gan_lambda, self.gan_lambda]
+        if self.ssim_lambda > 0:
+            terms.append(self._ssim_sum(recon_pairs, B))
+            lams.append(1.0)
         loss_all = ops.weighted_sum(terms, lams)
         preds = (ops.to_nchw(x1p), ops.to_nchw(x2p), ops.to_nchw(x3p))
         return ([torch.unsqueeze(loss_all, 0), xt_recon, x2t_recon, x3t_recon, z_kl, gan_seq,

@@ -19,6 +19,7 @@ Reference operators replaced (see include/vae2_hip.h for the kernel entry points
   cat         torch.cat on channels incl. code-map tiling :454-462, :818-830
   avgpool     nn.AdaptiveAvgPool2d((1, 1)) :1025
   l1          L1Loss criterion.py:61-69
+  ssim_loss   sum (1 - SSIM) reconstruction term (MI355X.SSIM_LAMBDA; not in the reference)
   reparam_kl  z = mu + exp(0.5 logvar) eps (utils.py:85-101) + KLLoss criterion.py:72-87
   lsgan       lsgan_adversarial_loss criterion.py:90-103
   split_frames  the discriminator's per-frame slices x[:, 3f:3f+3] (utils.py:116-118)
@@ -1693,6 +1694,68 @@ class _L1(torch.autograd.Function):
 def l1(pred, target, scale, flat=False):
     """scale * sum |pred - target| (NHWC views, or any dense layout with flat=True)."""
     return _L1.apply(pred, target, float(scale), flat)
+
+
+_SSIM_COEFFS = {}
+
+
+def ssim_coeffs(device, channels):
+    """(a, b) with a[c] = STD[c % 3], b[c] = MEAN[c % 3] (vae2.metrics): the de-normalisation
+    of stacked RGB frames to [0, 1].  Built once per (device, channels)."""
+    key = (str(device), int(channels))
+    ab = _SSIM_COEFFS.get(key)
+    if ab is None:
+        from .metrics import MEAN, STD
+        a = torch.tensor([STD[c % 3] for c in range(channels)], dtype=_F32).to(device)
+        b = torch.tensor([MEAN[c % 3] for c in range(channels)], dtype=_F32).to(device)
+        ab = _SSIM_COEFFS[key] = (a, b)
+    return ab
+
+
+class _SSIMLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, t, scale, a, b, c1, c2):
+        pp, pa = act_of(p)
+        tp, ta = act_of(t)
+        if (a is None) != (b is None):
+            raise ValueError("ssim_loss: a and b must be given together")
+        for coef in (a, b):
+            if coef is not None and (coef.dtype != _F32 or coef.device != p.device
+                                     or coef.numel() != pa.c or not coef.is_contiguous()):
+                raise ValueError("ssim_loss: a, b must be dense float32 [channels] tensors on "
+                                 "the predictions' device")
+        ws = _empty((_lib.load().vae2_ssim_loss_ws_size(ctypes.byref(pa)),), p, torch.float64)
+        out = _empty((), p)
+        call("vae2_ssim_loss_fwd", pp, ctypes.byref(pa), tp, ctypes.byref(ta), ptr(a), ptr(b),
+             c1, c2, scale, ptr(ws), ptr(out), stream_ptr())
+        ctx.consts = (scale, c1, c2)
+        ctx.save_for_backward(p, t, a, b)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        p, t, a, b = ctx.saved_tensors
+        scale, c1, c2 = ctx.consts
+        gout = gout.contiguous()
+        pp, pa = act_of(p)
+        tp, ta = act_of(t)
+        dp = new_act(tuple(p.shape), p)
+        dpp, da = act_of(dp)
+        call("vae2_ssim_loss_bwd", pp, ctypes.byref(pa), tp, ctypes.byref(ta), ptr(a), ptr(b),
+             c1, c2, ptr(gout), scale, dpp, ctypes.byref(da), 0.0, stream_ptr())
+        return dp, None, None, None, None, None, None
+
+
+def ssim_loss(pred, target, scale, a=None, b=None, c1=1e-4, c2=9e-4):
+    """scale * sum over images, channels and valid pixels of (1 - SSIM(a*pred + b,
+    a*target + b)) on NHWC views with sides >= 11: the 11-tap sigma-1.5 window of
+    vae2.metrics as a valid filter (include/vae2_hip.h has the formulas).  With
+    ssim_coeffs() and the default c1 = 0.01^2, c2 = 0.03^2 this is the evaluation's SSIM
+    (data_range 255) of the de-normalised [0, 1] images, except that _to_image's clip to
+    [0, 255] is deliberately not applied: a clip would zero the gradient exactly where a
+    prediction overshoots.  Only pred gets a gradient; the backward recomputes the maps
+    from pred and target, so nothing but those two is kept for it."""
+    return _SSIMLoss.apply(pred, target, float(scale), a, b, float(c1), float(c2))
 
 
 class _LSGAN(torch.autograd.Function):

@@ -7,7 +7,8 @@
                       clipping on (MI355X.CLIP_GRAD_NORM) the PRINT_FREQ points also
                       check and log the gradient norms: allreduce_grads runs before
                       step(), so a norm is that of the reduced gradient, identical on
-                      every rank.
+                      every rank.  With the SSIM terms on (MI355X.SSIM_LAMBDA) they also
+                      log the unweighted loss_x?t_ssim values.
   SyntheticClips      Cityscapes-shaped clips (3 segments x CLIP_LENGTH RGB frames
                       stacked on channels, cityscapes.py:311-326) for
                       benchmarking and CI; the zip/PNG clips are vae2/clips.py.
@@ -176,6 +177,10 @@ def adversarial_train(config, epoch, num_epoch, epoch_iters, base_lr, num_iters,
                           if ran and getattr(opt, "max_grad_norm", None) is not None]
             for _, val in grad_norms:
                 assert math.isfinite(val), "gradient norm got nan or inf"
+            # SSIM terms on (MI355X.SSIM_LAMBDA): this iteration's unweighted values
+            ssim_terms = getattr(fm, "ssim_terms", None) or ()
+            ssim_tags = ("xt", "x2t", "x3t") if len(ssim_terms) == 3 else ("x2t",)
+            ssim_vals = [(tag, float(t.item())) for tag, t in zip(ssim_tags, ssim_terms)]
         batch_time.update(time.time() - tic)
         tic = time.time()
         ave_loss_D.update(float(reduced_loss_D.item()))
@@ -197,6 +202,10 @@ def adversarial_train(config, epoch, num_epoch, epoch_iters, base_lr, num_iters,
                 logging.info(" ".join("grad_norm_{}: {:.6f}".format(t, v) for t, v in grad_norms))
                 for tag, val in grad_norms:
                     writer.add_scalar("train_grad_norm_" + tag, val, global_steps)
+            if ssim_vals:
+                logging.info(" ".join("loss_{}_ssim: {:.6f}".format(t, v) for t, v in ssim_vals))
+                for tag, val in ssim_vals:
+                    writer.add_scalar("train_loss_{}_ssim".format(tag), val, global_steps)
             for tag, val in (("train_loss_D", print_loss_D),
                              ("train_loss_D_sequence", f(loss_D_sequence)),
                              ("train_loss_D_frame", f(loss_D_frame)),
