@@ -234,7 +234,13 @@ int vae2_conv2d_bwd_weight_ld(const float* x, const vae2_act* xd, const float* d
 
 /* ------------------------------------------------------------ batchnorm ---- */
 /* nn.BatchNorm2d(momentum=0.01, eps=1e-5) in train mode, enc_hrnet.py:22-23,
- * (SyncBatchNorm when distributed, tools/train.py:216-218).                   */
+ * (SyncBatchNorm when distributed, tools/train.py:216-218).
+ * Shapes: every activation operand of one call (x, y, the residual, dy, dx, dres and, in
+ * the multi-layer calls, o, rx, rdx) has x's n, h, w and c; a call whose operands disagree
+ * is rejected with -22 before anything is launched (a multi-layer call: before its first
+ * launch, whichever layer disagrees).  One operand may say more: the multi-layer `a`
+ * (residual / stored y) may describe a wider tensor, ad.c >= xd.c, of which the first
+ * xd.c channels are used.  Descriptors of NULL operands are not looked at.            */
 
 /* Rows of partials written by vae2_bn_stats / vae2_bn_relu_bwd_reduce.        */
 int64_t vae2_bn_partial_rows(const vae2_act* xd);
@@ -357,7 +363,9 @@ typedef struct vae2_bn_layer {
   float* rdx; vae2_act rdxd;      /* backward apply: the residual BN's input gradient   */
   /* ABI 10: the ReLU mask as one byte per (pixel, channel quad), bit k = (y[4q+k] > 0),
    * [P][ceil(c/4)]: written by vae2_bn_multi_apply when non-NULL, read by the backward
-   * passes instead of y (a) -- 1/16 of y's bytes.  NULL: y / recomputed from x.         */
+   * passes instead of y (a) -- 1/16 of y's bytes.  NULL: y / recomputed from x.  The bits
+   * of channels >= c in the last quad's byte are unspecified (the forward computes them
+   * from whatever pads the pixel) and the backward passes ignore them.                 */
   unsigned char* mask;
 } vae2_bn_layer;
 /* y = relu?(fma(x, scale, shift) + a) per layer (vae2_bn_apply).                 */

@@ -1,6 +1,7 @@
 """Helpers shared by the kernel-level parity tests that call the C ABI directly
-(test_elbo_gpu.py, test_layout_pool_gpu.py): sentinel-padded device buffers for NHWC channel
-slices, bit comparison, and the three tolerance rules of those files."""
+(test_elbo_gpu.py, test_layout_pool_gpu.py, test_bn_gpu.py): sentinel-padded device buffers for
+NHWC channel slices and for flat buffers of any dtype, bit comparison, and the three tolerance
+rules of the first two files."""
 import ctypes
 
 import numpy as np
@@ -52,6 +53,28 @@ class Slice:
         outside = torch.cat([r[:self.lo], r[self.lo + self.pix * self.ps:],
                              body[:, :self.c0].reshape(-1), body[:, c1:].reshape(-1)])
         return bool((outside == self.sent).all())
+
+
+class Guarded:
+    """A device copy of a host tensor of any dtype (float partial rows, double sums, mask
+    bytes, an int64 counter), flattened, between GUARD sentinel elements of that dtype."""
+
+    def __init__(self, t, sent=None):
+        t = t.contiguous().view(-1)
+        self.sent = sent if sent is not None else (SENT if t.dtype.is_floating_point else 0x5A)
+        self.n = t.numel()
+        self.raw = torch.full((self.n + 2 * GUARD,), self.sent, dtype=t.dtype, device=DEV)
+        self.view = self.raw[GUARD:GUARD + self.n]
+        self.view.copy_(t)
+        self.ptr = ctypes.c_void_p(self.view.data_ptr())
+        self.addr = self.view.data_ptr()
+
+    def read(self):
+        return self.view.cpu()
+
+    def intact(self):
+        r = self.raw.cpu()
+        return bool((r[:GUARD] == self.sent).all()) and bool((r[GUARD + self.n:] == self.sent).all())
 
 
 def flat(x, offset=0):

@@ -1497,8 +1497,7 @@ int vae2_bn_apply(const float* x, const vae2_act* xd, const float* save,
                "x / y shape mismatch");
   Act r = to_act(yd);
   if (res) {
-    VAE2_REQUIRE(act_ok(rd) && rd->c == xd->c && rd->h == xd->h && rd->w == xd->w, fn,
-                 "residual shape mismatch");
+    VAE2_REQUIRE(act_ok(rd) && same_shape(rd, xd), fn, "residual shape mismatch");
     r = to_act(rd);
   }
   int64_t total = act_elems(xd);
@@ -1532,6 +1531,8 @@ int vae2_bn_relu_bwd_reduce(const float* dy, const vae2_act* dyd,
   const char* fn = "vae2_bn_relu_bwd_reduce";
   VAE2_REQUIRE(dy && x && save && partials && act_ok(dyd) && act_ok(xd), fn, "bad arguments");
   VAE2_REQUIRE(!y || act_ok(yd), fn, "bad y descriptor");
+  VAE2_REQUIRE(same_shape(dyd, xd), fn, "dy / x shape mismatch");
+  VAE2_REQUIRE(!y || same_shape(yd, xd), fn, "y / x shape mismatch");
   int64_t P = act_pixels(xd);
   int64_t ppb = pix_per_block(P, xd->c);
   Act ya = (relu && y) ? to_act(yd) : to_act(xd);
@@ -1568,6 +1569,10 @@ int vae2_bn_relu_bwd_apply(const float* dy, const vae2_act* dyd, const float* y,
                fn, "bad arguments");
   VAE2_REQUIRE(!y || act_ok(yd), fn, "bad y descriptor");
   VAE2_REQUIRE(!dres || act_ok(dresd), fn, "bad dres descriptor");
+  VAE2_REQUIRE(same_shape(dyd, xd), fn, "dy / x shape mismatch");
+  VAE2_REQUIRE(same_shape(dxd, xd), fn, "dx / x shape mismatch");
+  VAE2_REQUIRE(!y || same_shape(yd, xd), fn, "y / x shape mismatch");
+  VAE2_REQUIRE(!dres || same_shape(dresd, xd), fn, "dres / x shape mismatch");
   int64_t total = act_elems(xd);
   VAE2_REQUIRE(total < (int64_t(1) << 31), fn, "tensor too large");
   Act ya = (relu && y) ? to_act(yd) : to_act(xd);
@@ -1600,9 +1605,12 @@ static bool bn_layer_quad_ok(const vae2_bn_layer& l, bool bwd) {
               l.ad.c < x.c))
     return false;
   if (bwd) {
-    if (!l.dy || !v4_ok(l.dy, l.dyd.ps) || l.dyd.n != x.n || l.dyd.h != x.h || l.dyd.w != x.w)
+    if (!l.dy || !v4_ok(l.dy, l.dyd.ps) || l.dyd.n != x.n || l.dyd.h != x.h || l.dyd.w != x.w ||
+        l.dyd.c != x.c)
       return false;
-    if (l.dres && (!v4_ok(l.dres, l.dresd.ps) || l.dresd.c != x.c)) return false;
+    if (l.dres && (!v4_ok(l.dres, l.dresd.ps) || l.dresd.c != x.c || l.dresd.n != x.n ||
+                   l.dresd.h != x.h || l.dresd.w != x.w))
+      return false;
   }
   if (l.rx) {  // the residual BN's input (and its gradient): same pixels and channels
     const vae2_act& r = l.rxd;
@@ -1620,20 +1628,23 @@ static bool bn_layer_quad_ok(const vae2_bn_layer& l, bool bwd) {
 static int bn_multi_launch(int n, const vae2_bn_layer* ls, int kind, void* stream,
                            const char* fn) {
   VAE2_REQUIRE(n >= 0 && (n == 0 || ls), fn, "bad arguments");
+  for (int i = 0; i < n; ++i) {  // every layer before the first launch: a rejected call writes nothing
+    const vae2_bn_layer& l = ls[i];
+    VAE2_REQUIRE(bn_layer_quad_ok(l, kind != 0), fn,
+                 "layer tensors must be 16-byte aligned NHWC with pixel strides % 4 == 0, "
+                 "matching shapes, C <= 1024");
+    VAE2_REQUIRE(kind == 0 || (kind == 1 ? l.partials != nullptr : l.sums != nullptr), fn,
+                 "missing partials / sums");
+    VAE2_REQUIRE(!l.rx || kind == 0 || (kind == 1 ? l.rpartials != nullptr : l.rsums != nullptr),
+                 fn, "missing the residual BatchNorm's partials / sums");
+    VAE2_REQUIRE(kind != 2 || l.countp || l.count > 0, fn, "bad count");
+  }
   for (int i0 = 0; i0 < n; i0 += kBnMaxLayers) {
     BnMulti m{};
     m.n = n - i0 < kBnMaxLayers ? n - i0 : kBnMaxLayers;
     int blocks = 0;
     for (int j = 0; j < m.n; ++j) {
       const vae2_bn_layer& l = ls[i0 + j];
-      VAE2_REQUIRE(bn_layer_quad_ok(l, kind != 0), fn,
-                   "layer tensors must be 16-byte aligned NHWC with pixel strides % 4 == 0, "
-                   "matching shapes, C <= 1024");
-      VAE2_REQUIRE(kind == 0 || (kind == 1 ? l.partials != nullptr : l.sums != nullptr), fn,
-                   "missing partials / sums");
-      VAE2_REQUIRE(!l.rx || kind == 0 || (kind == 1 ? l.rpartials != nullptr : l.rsums != nullptr),
-                   fn, "missing the residual BatchNorm's partials / sums");
-      VAE2_REQUIRE(kind != 2 || l.countp || l.count > 0, fn, "bad count");
       BnLayer& L = m.L[j];
       L.x = l.x; L.a = l.a; L.o = l.o; L.dy = l.dy; L.dres = l.dres; L.part = l.partials;
       L.save = l.save; L.gamma = l.gamma; L.sums = l.sums; L.countp = l.countp;
