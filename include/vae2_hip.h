@@ -77,27 +77,10 @@ int vae2_conv2d_set_algo(int algo);
  * optimizer stay fp32).  Returns the previous setting.  Process-wide.             */
 int vae2_conv2d_set_mfma_bf16(int on);
 /* Launch-shape tuning knobs for A/B measurements (every setting computes the same
- * result): key 0 = minimum igemm workgroups (row tiles shrink 4 -> 2 -> 1 until the grid
- * reaches it; default 512, 0 = the 4-row-tile rule alone); key 1 = 1: weight gradients with 64 (tap, Cin4)
- * columns take 2 x 16 output-channel rows and all 64 columns per workgroup (not 4 x 16
- * rows and 48 + 48 columns); key 2 = 1: the direct 3x3 kernels' 8-row tiles run as 8
- * waves of one row each (512 threads) instead of 4 waves of two rows; key 3 = 1: the
- * 18 / 36 / 72-channel 3x3 weight gradients spread their column tiles over 8 waves;
- * key 4 = the persistent 1x1 GEMM's maximum N tiles (of 16 channels) per workgroup, 3..8
- * (default 4); key 5 = 1: its row tiles of 16 instead of 32 pixels; key 6 = 1: gather-GEMM
- * convs with 18 / 36 output channels as 16 + 2 / 32 + 4 (VALU remainder columns); keys
- * 7-13: see vae2_conv2d_set_tune in csrc/conv.hip; key 14 = 1: the 72-channel direct 3x3
- * as two N blocks of 32 + 4 (off: measured slower); key 15 = 1 (default): direct 3x3
- * layers whose 4-row tiles leave <= 2 workgroups per CU split K over 8-wave workgroups
- * (2 = over 16-wave workgroups, 4 shares; 0 = off);
- * key 16 = the narrow 3x3 weight gradient's minimum tiles per partial slab (1..2, default 2);
- * key 17 = the streaming 3x3's minimum 4-row steps per band (1..2, default 1); key 18 = the
- * gather weight gradient's target workgroups (256..8192, default 1024); key 19 = BatchNorm
- * blocks per layer at most (256..8192, default 1024); key 20 = the multi-layer BatchNorm
- * apply kernels' resident-block budget (0 = one workgroup per pixel chunk, the default; R > 0:
- * ceil(T / ceil(T / R)) workgroups stride over the T chunks); key 21 = 0: the fuse sum +
- * ReLU one channel per thread instead of one channel quad (default 1).  Returns the previous value, -1 for an unknown key or an
- * out-of-range value of keys 4, 6, 7 and 15-20 (the setting is then left unchanged).    */
+ * result), keys 0..21.  The table kKnobs in csrc/conv.hip lists each key with what it
+ * does, its default, the values it accepts and what happens to any other value (stored as a
+ * fixed substitute, or refused).  Returns the previous value, or -1 for an unknown key or a
+ * refused value (keys 4, 6, 7 and 15-20; the setting is then left unchanged).       */
 int vae2_conv2d_set_tune(int key, int value);
 /* Deferred weight-gradient reductions: while on (a per-thread switch), every
  * vae2_conv2d_bwd_weight(_ld) launches its partial-slab kernel and queues the slab

@@ -17,32 +17,20 @@ TAG = os.environ.get("VAE2_BUILD_TAG", "")
 DEFS = os.environ.get("VAE2_DEFS", "").split()
 OUT = os.path.join(PKG, f"libvae2_hip_{TAG}.so" if TAG else "libvae2_hip.so")
 BUILD = os.path.join(HERE, f"build_{TAG}" if TAG else "build")
-SOURCES = ["conv.hip", "bn.hip", "resample.hip", "elbo.hip", "heads.hip", "clips.hip",
-           "metrics.hip", "wgrad_narrow.hip", "syncbn.hip", "dconv_stream.hip",
-           "ssim_loss.hip"]
-HEADERS = ["common.h", os.path.join("..", "..", "include", "vae2_hip.h")]
+CONV = ["conv.hip", "conv_gather.hip", "conv_direct.hip", "conv_wgrad.hip"]
+SOURCES = CONV + ["bn.hip", "resample.hip", "elbo.hip", "heads.hip", "clips.hip", "metrics.hip",
+                  "wgrad_narrow.hip", "syncbn.hip", "dconv_stream.hip", "ssim_loss.hip"]
+HEADERS = ["common.h", "conv.h", os.path.join("..", "..", "include", "vae2_hip.h")]
 ARCH = os.environ.get("VAE2_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
          "-Wno-unused-function", "-munsafe-fp-atomics"]
 # per-source extras: no SLP vectorisation in the conv kernels (it packs independent f32
 # FMAs beside the MFMAs into v_pk_fma_f32 + operand moves, which cost issue slots there)
-EXTRA = {"conv.hip": ["-fno-slp-vectorize"], "dconv_stream.hip": ["-fno-slp-vectorize"]}
-# conv.hip is compiled as four objects (VAE2_CONV_PART 0..3: pack + C-ABI dispatch, gather
-# kernels, direct 3x3 kernels, weight-gradient kernels) so its instantiations build in
-# parallel
-PARTS = {"conv.hip": 4}
+EXTRA = {src: ["-fno-slp-vectorize"] for src in CONV + ["dconv_stream.hip"]}
 
 
 def _units():
-    out = []
-    for src in SOURCES:
-        n = PARTS.get(src, 0)
-        base = os.path.splitext(src)[0]
-        if n:
-            out += [(src, f"{base}_p{i}.o", [f"-DVAE2_CONV_PART={i}"]) for i in range(n)]
-        else:
-            out.append((src, base + ".o", []))
-    return out
+    return [(src, os.path.splitext(src)[0] + ".o") for src in SOURCES]
 
 
 def hipcc():
@@ -60,12 +48,12 @@ def _newer(target, deps):
 
 
 def _compile(unit):
-    src, oname, defs = unit
+    src, oname = unit
     obj = os.path.join(BUILD, oname)
     deps = [os.path.join(HERE, src)] + [os.path.join(HERE, h) for h in HEADERS]
     if not _newer(obj, deps):
         return obj, None
-    cmd = [hipcc()] + FLAGS + EXTRA.get(src, []) + defs + DEFS + ["-c", os.path.join(HERE, src), "-o", obj]
+    cmd = [hipcc()] + FLAGS + EXTRA.get(src, []) + DEFS + ["-c", os.path.join(HERE, src), "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         return obj, f"$ {' '.join(cmd)}\n{r.stdout}\n{r.stderr}"

@@ -2,7 +2,7 @@
 // 36 -> 36 channels (enc_hrnet.py:27-30 conv3x3 inside BasicBlock, :33-62), forward and
 // data gradient (the transposed conv, weights packed mode 1 and taps flipped).
 //
-// dconv3_kernel (conv.hip) gives each workgroup one 8 x 32 output tile: it stages the
+// dconv3_kernel (conv_direct.hip) gives each workgroup one 8 x 32 output tile: it stages the
 // 10 x 34 halo tile, waits, runs the MFMA loop, writes, and exits -- at 18 channels the
 // staging, the barrier and the epilogue are a third of the kernel, never overlapped with
 // the matrix cores, and the halo rows are loaded twice (1.33x the input bytes).  Here a
@@ -33,7 +33,7 @@
 // BatchNorm's backward partials (sum g, sum g*xhat) in the epilogue instead of (sum, sum^2)).
 #include <type_traits>
 
-#include "common.h"
+#include "conv.h"
 
 namespace vae2 {
 
@@ -552,7 +552,7 @@ int dconv3s_launch(const float* a, const vae2_act* ad, const float* wp, uint32_t
   p.tiles_w = d.tiles_w; p.nbands = d.nbands; p.band_rows = d.band_rows;
   p.w = wp; p.a_bytes = a_bytes; p.w_bytes = w_bytes;
   p.n = (int)yd->c; p.bias = bias; p.y = y; p.y_ps = (int)yd->ps; p.beta = beta;
-  // (the extent act_bytes in conv.hip gives: the last pixel's channels, its padded quad
+  // (the extent act_bytes in conv.h gives: the last pixel's channels, its padded quad
   //  when the pixel stride is a multiple of 4)
   const int64_t ytail = (yd->ps % 4 == 0) ? (yd->c + 3) / 4 * 4 : yd->c;
   p.y_bytes = (uint32_t)(((yd->n * yd->h * yd->w - 1) * yd->ps + ytail) * 4);

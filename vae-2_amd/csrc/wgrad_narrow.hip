@@ -4,7 +4,7 @@
 //   dW[co][ci][dh][dw] = sum_px dY[px][co] * X[px + (dh-1, dw-1)][ci]
 //
 // GEMM view: M = co (16*TM on MFMA + NR <= 4 on the VALU), K = output pixels, N = the 9*ci
-// (tap, channel) columns.  wgrad3_kernel (conv.hip) orders the columns (tap, ci) and reads
+// (tap, channel) columns.  wgrad3_kernel (conv_wgrad.hip) orders the columns (tap, ci) and reads
 // every B fragment (4 consecutive pixels of one column) as four unaligned LDS words.  Here
 // the columns are ordered (dw, dh, ci) with every dw group padded to whole 16-column tiles:
 // lane (r, g) of column tile (j, dw) holds column (dh, ci) = divmod(16 j + r, CSW) for all
@@ -20,11 +20,10 @@
 // computes.  WPIX waves split the tile's 16-pixel chunks, the remaining factor 4 / WPIX
 // splits the column groups; waves holding the same columns are summed through LDS at the
 // end in a fixed order (deterministic).
-#include "common.h"
+#include "conv.h"
 
 namespace vae2 {
 
-extern int g_bf16, g_wgrad_narrow;
 int g_wgrad_narrow_tps = 2;  // vae2_conv2d_set_tune key 16: minimum tiles per split (1 or 2)
 
 // (the kernel is an exported symbol, outside the anonymous namespace: the launch log
@@ -428,7 +427,7 @@ bool plan(const vae2_act* xd, const vae2_act* dyd, Plan& pl) {
 }  // namespace
 
 // Partial-slab rows (splits) the narrow kernel writes for this layer, 0 when it does not
-// apply (conv.hip sizes the workspace with the larger of the two forms).
+// apply (conv_wgrad.hip sizes the workspace with the larger of the two forms).
 int64_t wgrad3n_splits(const vae2_act* xd, const vae2_act* dyd) {
   Plan pl;
   return plan(xd, dyd, pl) ? pl.splits : 0;
