@@ -114,10 +114,8 @@ def _lazy_pair(x, conv_a, bn_a, conv_b, bn_b, x_link=None, part=None):
     bn1 -> conv2 (enc_hrnet.py:84-90) and the stem's bn1 -> conv2 (:788-793); otherwise its
     backward partials come from conv_b's data gradient (ops.PartBN).  part: bn_b's PartBN
     (its output's only consumer takes it as bn_part), or None."""
-    n, h, w, _ = x.shape
-    spec = ops.ConvSpec(conv_a)
-    oh, ow = spec.out_hw(h, w)
-    lz = ops.LazyBN() if ops.lazy_bn_ok((n, oh, ow, conv_a.out_channels), conv_b) else None
+    oh, ow = ops.ConvSpec(conv_a).out_hw(*x.shape[1:3])
+    lz = ops.LazyBN() if ops.lazy_bn_ok((x.shape[0], oh, ow, conv_a.out_channels), conv_b) else None
     if lz is None and ops.PART_BN:
         lz = ops.PartBN()
     lazy = [lz]
@@ -286,16 +284,13 @@ class HighResolutionModule(nn.Module):
             lz_dn = [ops.LazyBN() if ops.FUSE_LAZY and k == i - j - 1 else
                      (ops.PartBN() if ops.PART_BN and k < i - j - 1 else None)
                      for i, j in live]
-            ins = [parts.get(ij) for ij in live]
             outs = _run_convbn_seqs([self.fuse_layers[i][j][k] for i, j in live],
                                     [cur[ij] for ij in live],
                                     [links[j] if k == 0 else None for _, j in live], lz_dn,
-                                    bn_ins=ins if any(b is not None for b in ins) else None)
+                                    bn_ins=[parts.get(ij) for ij in live])
             parts = {ij: lz for ij, lz in zip(live, lz_dn) if isinstance(lz, ops.PartBN)}
             cur.update(zip(live, outs))
-            lazy.update((ij, lz) for ij, lz in zip(live, lz_dn)
-                        if not isinstance(lz, ops.PartBN) and (lz is not None or
-                                                               k == ij[0] - ij[1] - 1))
+            lazy.update((ij, lz) for ij, lz in zip(live, lz_dn) if isinstance(lz, ops.LazyBN))
         terms.update(cur)
         out = []
         for i, _ in rows:

@@ -25,7 +25,10 @@ Reference operators replaced (see include/vae2_hip.h for the kernel entry points
   split_frames  the discriminator's per-frame slices x[:, 3f:3f+3] (utils.py:116-118)
   weighted_sum  loss assembly utils.py:150-152
 """
+import collections
 import ctypes
+import functools
+import itertools
 
 import torch
 import torch.distributed as dist
@@ -135,42 +138,74 @@ class GradLink:
         buf, self.buf = self.buf, None
         return buf
 
+    def hand_over(self, g, before_add=None):
+        """A consumer's finished contribution g becomes the shared buffer, is added onto it
+        (after before_add(buf): the caller settles pending writers) or already is it; finish()."""
+        if self.buf is None:
+            self.buf = g
+        elif self.buf is not g:
+            if before_add is not None:
+                before_add(self.buf)
+            self.buf.add_(g)
+        return self.finish()
+
 
 # ------------------------------------------------- BN fused into the consumer ----
-class LazyBN:
-    """A training-mode BatchNorm(+ReLU) layer whose normalised output z is never stored
-    (BasicBlock's bn1 -> relu -> conv2, enc_hrnet.py:46-55): its _ConvBNMulti level
-    returns the pre-BN conv output r in z's place, the consumer conv normalises r while
-    staging its input (vae2_conv2d_fwd_bnin; the weight gradient likewise,
-    vae2_conv2d_bwd_weight_bnin), and the consumer's data gradient -- the gradient of z
-    -- writes this layer's backward partials in its epilogue
-    (vae2_conv2d_bwd_data_bnpart), so neither the forward apply pass nor the backward
-    reduce pass runs for it.  `save` = the layer's (mean, invstd, scale, shift)."""
+class _BNMarker:
+    """Hand-off between a BatchNorm layer of a _ConvBNMulti level and the ONE consumer of its
+    output (marker protocol): the consumer's entry point calls claim(), the producer's
+    forward publish() (save = (mean, invstd, scale, shift), r = its pre-BN tensor or None), the
+    consumer's data gradient put_partials() and the producer's backward take_partials()."""
 
-    __slots__ = ("save", "relu", "part", "rows")
+    __slots__ = ("save", "relu", "part", "rows", "r", "claimed")
 
     def __init__(self):
-        self.save, self.relu, self.part, self.rows = None, False, None, 0
+        self.claimed = False
+        self.publish(None, False)
+
+    def claim(self):
+        if self.claimed:
+            raise RuntimeError("one consumer per marked BatchNorm output: already claimed")
+        self.claimed = True
+
+    def publish(self, save, relu, r=None):
+        self.save, self.relu, self.r, self.part, self.rows = save, relu, r, None, 0
+
+    def put_partials(self, part, rows):
+        self.part, self.rows = part, rows
+
+    def take_partials(self):
+        """(part, rows); the buffer is released, `rows` stays (tests count the hand-offs)."""
+        part, self.part = self.part, None
+        return part, self.rows
+
+
+def _claim(markers):
+    for m in markers or ():
+        if isinstance(m, _BNMarker):
+            m.claim()
+
+
+class LazyBN(_BNMarker):
+    """A training-mode BatchNorm(+ReLU) layer whose normalised output z is never stored
+    (BasicBlock's bn1 -> relu -> conv2, enc_hrnet.py:46-55): its level returns the pre-BN conv
+    output r in z's place, the consumer conv normalises r while staging its input
+    (vae2_conv2d_fwd_bnin, vae2_conv2d_bwd_weight_bnin) and its data gradient writes this
+    layer's backward partials (vae2_conv2d_bwd_data_bnpart): no apply and no reduce pass."""
+    __slots__ = ()
 
 
 LAZY_BN = True  # False: every BatchNorm output is stored (A/B and parity tests)
 
 
-class PartBN:
+class PartBN(_BNMarker):
     """A training-mode BatchNorm(+ReLU) layer without residual whose STORED output y feeds
-    exactly one conv that cannot normalise lazily (a 1x1 GEMM, a gather-kernel conv, a
-    stride-2 conv): the Bottleneck's bn2 -> conv3 (enc_hrnet.py:84-101), the 144-channel
-    branch's BasicBlock bn1 -> conv2, the inner units of a fuse down-chain (:199-218).  The
-    forward is unchanged; the consumer's data gradient -- the gradient of y, complete because
-    y has no other consumer -- writes this layer's backward partials (sum g, sum g*xhat) in
-    its epilogue (vae2_conv2d_bwd_data_bnpart, every kernel family since round 6), so the
-    layer's backward reduce pass does not run.  r = the layer's pre-BN tensor (the ReLU mask
-    is recomputed from it), save = its (mean, invstd, scale, shift)."""
-
-    __slots__ = ("save", "relu", "part", "rows", "r")
-
-    def __init__(self):
-        self.save, self.relu, self.part, self.rows, self.r = None, False, None, 0, None
+    exactly one conv that cannot normalise lazily (a 1x1 GEMM, a gather-kernel or stride-2 conv:
+    the Bottleneck's bn2 -> conv3, the 144-channel BasicBlock's bn1 -> conv2, the inner units of
+    a fuse down-chain).  The forward is unchanged; the consumer's data gradient writes this
+    layer's backward partials in its epilogue (vae2_conv2d_bwd_data_bnpart; the ReLU mask
+    recomputed from r), so the layer's backward reduce pass does not run."""
+    __slots__ = ()
 
 
 PART_BN = True  # False: the layers above run their own backward reduce pass (A/B, tests)
@@ -178,12 +213,10 @@ PART_BN = True  # False: the layers above run their own backward reduce pass (A/
 
 class ResBN:
     """Marks a layer of a _ConvBNMulti level whose BatchNorm output (no ReLU) is only the
-    residual of another layer of the same level (the Bottleneck's downsample shortcut,
-    enc_hrnet.py:94-101): that layer's apply adds it as fma(r, scale, shift) and its
-    backward kernels produce this BN's partials and input gradient from the same masked
-    gradient (vae2_bn_layer.rx ...), so the shortcut's BN output is never stored and its
-    three BN passes do not run."""
-
+    residual of another layer of the level (the Bottleneck's downsample shortcut,
+    enc_hrnet.py:94-101): that layer's apply adds it as fma(r, scale, shift) and its backward
+    kernels produce this BN's partials and input gradient from the same masked gradient
+    (vae2_bn_layer.rx ...): the shortcut's BN output is never stored, its BN passes never run."""
     __slots__ = ()
 
 
@@ -355,21 +388,6 @@ def _conv_work(kind, xa, yshape, k, stride):
               prof.conv_label(kind, xa.c, cout, k, stride, xa.h, xa.w))
 
 
-def _conv_fwd(x, weight, bias, spec, stats=None):
-    xp, xa = act_of(x)
-    n, h, w, _ = x.shape
-    oh, ow = spec.out_hw(h, w)
-    cout = weight.shape[0]
-    y = new_act((n, oh, ow, cout), x)
-    yp, ya = act_of(y)
-    wp = packed_weight(weight, 0)
-    if prof.active():
-        _conv_work("fwd", xa, (n, oh, ow, cout), spec.k, spec.stride)
-    call("vae2_conv2d_fwd", xp, ctypes.byref(xa), ptr(wp), ptr(bias), yp, ctypes.byref(ya),
-         spec.k, spec.stride, spec.pad, 0.0, ptr(stats), stream_ptr())
-    return y
-
-
 class ConvGroup:
     """Independent convolutions of one depth level queued and issued by one
     vae2_conv2d_multi call (direct-3x3 layers share launches).  Tensors a queued job
@@ -416,10 +434,10 @@ def _merge(notes):
             " + ".join(n[2] for n in notes if n[2]))
 
 
-def _conv_fwd_queued(group, x, weight, bias, spec, stats, sp=None):
-    """_conv_fwd, queued on a ConvGroup (a LazyBN input: launched at once, normalised
-    while staged).  group None: launched at once on stream sp (a level lane, see
-    _Lanes); the output is allocated on the current stream either way."""
+def _conv_fwd(x, weight, bias, spec, stats=None, group=None, sp=None):
+    """The conv's forward into a fresh output, its epilogue writing the BN statistics partials
+    `stats`: launched at once on stream sp (a level lane, _Lanes; default: the current stream;
+    vae2_conv2d_fwd_bnin for a LazyBN input, normalised while staged) or queued on `group`."""
     sp = stream_ptr() if sp is None else sp
     xp, xa = act_of(x)
     n, h, w, _ = x.shape
@@ -427,19 +445,17 @@ def _conv_fwd_queued(group, x, weight, bias, spec, stats, sp=None):
     cout = weight.shape[0]
     y = new_act((n, oh, ow, cout), x)
     yp, ya = act_of(y)
+    wp, lz = packed_weight(weight, 0), spec.bn_in
     if prof.active():
         _conv_work("fwd", xa, (n, oh, ow, cout), spec.k, spec.stride)
-    lz = spec.bn_in
     if lz is not None:
-        call("vae2_conv2d_fwd_bnin", xp, ctypes.byref(xa), ptr(lz.save), int(lz.relu),
-             ptr(packed_weight(weight, 0)), ptr(bias), yp, ctypes.byref(ya), spec.k,
-             spec.stride, spec.pad, 0.0, ptr(stats), sp)
-        return y
-    if group is None:
-        call("vae2_conv2d_fwd", xp, ctypes.byref(xa), ptr(packed_weight(weight, 0)), ptr(bias),
-             yp, ctypes.byref(ya), spec.k, spec.stride, spec.pad, 0.0, ptr(stats), sp)
-        return y
-    group.add(0, xp, xa, packed_weight(weight, 0), bias, yp, ya, spec, 0.0, stats)
+        call("vae2_conv2d_fwd_bnin", xp, ctypes.byref(xa), ptr(lz.save), int(lz.relu), ptr(wp),
+             ptr(bias), yp, ctypes.byref(ya), spec.k, spec.stride, spec.pad, 0.0, ptr(stats), sp)
+    elif group is None:
+        call("vae2_conv2d_fwd", xp, ctypes.byref(xa), ptr(wp), ptr(bias), yp, ctypes.byref(ya),
+             spec.k, spec.stride, spec.pad, 0.0, ptr(stats), sp)
+    else:
+        group.add(0, xp, xa, wp, bias, yp, ya, spec, 0.0, stats)
     return y
 
 
@@ -553,114 +569,132 @@ class _defer_off:
 def _conv_bwd(x, weight, bias, dy, spec, need_dx, need_w=True, need_b=True, group=None,
               sp=None, hold=None):
     """dW/db accumulated into sinks; returns (dx or None, grad for W, grad for b).  With a
-    ConvGroup the data gradient is queued on it (dx is complete once it is flushed).  An
-    input marked `_vae2_no_dx` (vae2.dist.anchor_reduce's output when its source needs no
-    gradient) gets none: it requires grad only to route the anchor's backward.
-    sp: launch on this stream (a level lane, _Lanes) while allocating on the current one;
-    the weight-gradient reduction then runs at once on the lane (not deferred: the deferred
-    queue is keyed by launch stream) and the workspaces go to `hold`, which the caller keeps
-    until the lane has joined."""
-    lane = sp is not None
+    ConvGroup the data gradient is queued on it (complete once it is flushed).  An input marked
+    `_vae2_no_dx` (vae2.dist.anchor_reduce's output when its source needs no gradient) gets none.
+    sp: launch on this stream (a level lane, _Lanes) while allocating on the current one; the
+    workspaces then go to `hold`, which the caller keeps until the lane has joined."""
     s = stream_ptr() if sp is None else sp
-    xp, xa = act_of(x)
-    dyp, dya = act_of(dy)
+    xv, dyv = act_of(x), act_of(dy)  # (ws: the workspace stays allocated during the dgrad)
+    wret, bret, ws = _conv_wgrad(x, xv, weight, bias, dy, dyv, spec, need_w, need_b, s=s,
+                                 lane=sp is not None, hold=hold)
+    if not need_dx or getattr(x, "_vae2_no_dx", False):
+        return None, wret, bret
+    return _conv_dgrad(x, xv, weight, dy, dyv, spec, group=group, s=s, hold=hold), wret, bret
+
+
+def _conv_wgrad(x, xv, weight, bias, dy, dyv, spec, need_w, need_b, *, s, lane, hold):
+    """vae2_conv2d_bwd_weight(_bnin for a LazyBN input) on stream s; on a lane the reduction runs
+    at once (the deferred queue is keyed by launch stream).  Returns (dW, db, workspace)."""
+    (xp, xa), (dyp, dya) = xv, dyv
     wsink, wret = _grad_sink(weight, need_w)
     bsink, bret = _grad_sink(bias, need_b)
-    if wsink is not None or bsink is not None:
-        tmp_w = wsink is None
-        if tmp_w:  # weight frozen but bias trained: still need a dW target
-            wsink = torch.zeros_like(weight)
-        size = _lib.load().vae2_conv2d_bwd_weight_ws_size(ctypes.byref(xa), ctypes.byref(dya),
-                                                          spec.k)
-        ws = _empty((max(size, 1),), x)
-        if prof.active():
-            _conv_work("wgrad", xa, tuple(dy.shape), spec.k, spec.stride)
-        lz = spec.bn_in
-        now = wret is not None or tmp_w or lane  # not a main_grad view: reduce before returning
-        if lane and hold is not None:
-            hold.append(ws)
-        with _defer_off(now and _WGRAD_BATCH[0] > 0):
-            if lz is not None:
-                call("vae2_conv2d_bwd_weight_bnin", xp, ctypes.byref(xa), ptr(lz.save),
-                     int(lz.relu), dyp, ctypes.byref(dya), ptr(wsink), ptr(bsink), spec.k,
-                     spec.stride, spec.pad, 1, ptr(ws), size, s)
-            else:
-                call("vae2_conv2d_bwd_weight", xp, ctypes.byref(xa), dyp, ctypes.byref(dya),
-                     ptr(wsink), ptr(bsink), spec.k, spec.stride, spec.pad, 1, ptr(ws), size, s)
-        if _WGRAD_BATCH[0] and not now:  # the deferred reduction reads it at the flush
-            _WS_HOLD.append((torch.cuda.current_stream().cuda_stream, ws))
-    dx = None
-    if need_dx and not getattr(x, "_vae2_no_dx", False):
-        link = spec.x_link
-        beta = 0.0
-        if link is not None and link.buf is not None:
-            dx, beta = link.buf, 1.0  # accumulate onto the other consumer's contribution
+    if wsink is None and bsink is None:
+        return wret, bret, None
+    tmp_w = wsink is None
+    if tmp_w:  # weight frozen but bias trained: still need a dW target
+        wsink = torch.zeros_like(weight)
+    size = _lib.load().vae2_conv2d_bwd_weight_ws_size(ctypes.byref(xa), ctypes.byref(dya), spec.k)
+    ws = _empty((max(size, 1),), x)
+    if prof.active():
+        _conv_work("wgrad", xa, tuple(dy.shape), spec.k, spec.stride)
+    lz = spec.bn_in
+    now = wret is not None or tmp_w or lane  # not a main_grad view: reduce before returning
+    if lane and hold is not None:
+        hold.append(ws)
+    with _defer_off(now and _WGRAD_BATCH[0] > 0):
+        if lz is not None:
+            call("vae2_conv2d_bwd_weight_bnin", xp, ctypes.byref(xa), ptr(lz.save),
+                 int(lz.relu), dyp, ctypes.byref(dya), ptr(wsink), ptr(bsink), spec.k,
+                 spec.stride, spec.pad, 1, ptr(ws), size, s)
         else:
-            dx = new_act(tuple(x.shape), x)
-            if link is not None:
-                link.buf = dx
-        dxp, dxa = act_of(dx)
-        wp = packed_weight(weight, 1)
-        if prof.active():
-            _conv_work("dgrad", xa, tuple(dy.shape), spec.k, spec.stride)
-        lz = spec.bn_in
-        pb = spec.bn_part
-        if pb is not None and (pb.r is None or pb.save is None or link is not None):
-            pb = None  # the producer stored no pre-BN tensor, or x has another consumer
-        rows = 0
-        if (lz is not None or pb is not None) and beta == 0.0:
-            rows = _lib.load().vae2_conv2d_bwd_data_bnpart_rows(
-                dyp, ctypes.byref(dya), ctypes.byref(dxa), spec.k, spec.stride, spec.pad)
-        if rows > 0:  # + the producer layer's backward partials (its reduce pass skipped)
-            part = _empty((2 * rows * xa.c,), x)
-            if hold is not None:
-                hold.append(part)
-            src = lz if lz is not None else pb
-            # the producer's pre-BN tensor: x itself for a LazyBN input, r for a PartBN one
-            bxp, bxa = (xp, xa) if lz is not None else act_of(pb.r)
-            call("vae2_conv2d_bwd_data_bnpart", dyp, ctypes.byref(dya), ptr(wp), dxp,
-                 ctypes.byref(dxa), spec.k, spec.stride, spec.pad, bxp, ctypes.byref(bxa),
-                 ptr(src.save), int(src.relu), ptr(part), s)
-            src.part, src.rows = part, rows
-        elif group is not None:
-            group.add(1, dyp, dya, wp, None, dxp, dxa, spec, beta)
-        else:
-            call("vae2_conv2d_bwd_data", dyp, ctypes.byref(dya), ptr(wp), dxp,
-                 ctypes.byref(dxa), spec.k, spec.stride, spec.pad, beta, s)
+            call("vae2_conv2d_bwd_weight", xp, ctypes.byref(xa), dyp, ctypes.byref(dya),
+                 ptr(wsink), ptr(bsink), spec.k, spec.stride, spec.pad, 1, ptr(ws), size, s)
+    if _WGRAD_BATCH[0] and not now:  # the deferred reduction reads it at the flush
+        _WS_HOLD.append((torch.cuda.current_stream().cuda_stream, ws))
+    return wret, bret, ws
+
+
+def _conv_dgrad(x, xv, weight, dy, dyv, spec, *, group, s, hold):
+    """The data gradient into a fresh buffer or onto spec.x_link's (None while other consumers
+    are to come): vae2_conv2d_bwd_data on stream s or queued on `group`, or _bnpart, which also
+    writes the backward partials of the BatchNorm layer that produced x (put_partials)."""
+    (xp, xa), (dyp, dya) = xv, dyv
+    link, beta = spec.x_link, 0.0
+    if link is not None and link.buf is not None:
+        dx, beta = link.buf, 1.0  # accumulate onto the other consumer's contribution
+    else:
+        dx = new_act(tuple(x.shape), x)
         if link is not None:
-            dx = link.finish()
-    return dx, wret, bret
+            link.buf = dx
+    (dxp, dxa), wp = act_of(dx), packed_weight(weight, 1)
+    if prof.active():
+        _conv_work("dgrad", xa, tuple(dy.shape), spec.k, spec.stride)
+    lz, src = spec.bn_in, spec.bn_in if spec.bn_in is not None else spec.bn_part
+    if lz is None and src is not None and (src.r is None or src.save is None or
+                                           link is not None):
+        src = None  # the PartBN producer stored no pre-BN tensor, or x has another consumer
+    rows = 0
+    if src is not None and beta == 0.0:
+        rows = _lib.load().vae2_conv2d_bwd_data_bnpart_rows(
+            dyp, ctypes.byref(dya), ctypes.byref(dxa), spec.k, spec.stride, spec.pad)
+    if rows > 0:  # + the producer layer's backward partials (its reduce pass skipped)
+        part = _empty((2 * rows * xa.c,), x)
+        if hold is not None:
+            hold.append(part)
+        # the producer's pre-BN tensor: x itself for a LazyBN input, r for a PartBN one
+        bxp, bxa = (xp, xa) if lz is not None else act_of(src.r)
+        call("vae2_conv2d_bwd_data_bnpart", dyp, ctypes.byref(dya), ptr(wp), dxp,
+             ctypes.byref(dxa), spec.k, spec.stride, spec.pad, bxp, ctypes.byref(bxa),
+             ptr(src.save), int(src.relu), ptr(part), s)
+        src.put_partials(part, rows)
+    elif group is not None:
+        group.add(1, dyp, dya, wp, None, dxp, dxa, spec, beta)
+    else:
+        call("vae2_conv2d_bwd_data", dyp, ctypes.byref(dya), ptr(wp), dxp,
+             ctypes.byref(dxa), spec.k, spec.stride, spec.pad, beta, s)
+    return link.finish() if link is not None else dx
+
+
+# One conv -> BN layer's autograd inputs, in _ConvBN.apply's and (per layer) _ConvBNMulti's order
+_In = collections.namedtuple("_In", "x weight bias gamma beta residual")
+
+
+def _layer_needs(need, i):
+    """needs_input_grad of layer i of a _ConvBNMulti level (need[0]: specs), by input name."""
+    k = len(_In._fields)
+    return _In(*need[1 + k * i:1 + k * (i + 1)])
+
+
+def _level_grads(per_layer):
+    """_ConvBNMulti.backward's return value from one _In of gradients per layer."""
+    return (None, *itertools.chain.from_iterable(per_layer))
+
+
+def _running_ptrs(bn):
+    """Addresses of the running statistics a training-mode finalize updates (or nulls)."""
+    if bn.track_running_stats and bn.running_mean is not None:
+        return ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked)
+    return None, None, None
 
 
 class _ConvBN(torch.autograd.Function):
+    """Single-layer BN entry points: eval mode, and training with a residual not 16-B aligned."""
+
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, residual, spec):
-        lib = _lib.load()
         s = stream_ptr()
-        bn = spec.bn
-        n, h, w, _ = x.shape
-        oh, ow = spec.out_hw(h, w)
-        cout = weight.shape[0]
-        count = float(n * oh * ow)
-        group = None
+        bn, group = spec.bn, None
+        L = _Layer(spec, _In(x, weight, bias, gamma, beta, residual))
+        r, stats, cout, count, rows = L.conv(stats=spec.training), L.stats, L.cout, L.count, L.rows
         if spec.training:
-            xp, xa = act_of(x)
-            rows = lib.vae2_conv2d_fwd_stats_rows(xp, ctypes.byref(xa),
-                                                  ctypes.byref(Act(n, oh, ow, cout, cout)),
-                                                  spec.k, spec.stride, spec.pad)
-            stats = _empty((2 * rows * cout,), x)
-            r = _conv_fwd(x, weight, bias, spec, stats)
             sums = _empty((2 * cout,), x, torch.float64)
             group = _bn_group()
             save = _empty((4 * cout,), x)
-            track = bn.track_running_stats and bn.running_mean is not None
-            stat_ptrs = (ptr(bn.running_mean) if track else None,
-                         ptr(bn.running_var) if track else None,
-                         ptr(bn.num_batches_tracked) if track else None)
+            stat_ptrs = _running_ptrs(bn)
             if group is None:
                 if count <= 1:
                     raise ValueError("Expected more than 1 value per channel when training, "
-                                     f"got input size {(n, cout, oh, ow)}")
+                                     f"got input size {(x.shape[0], cout, *r.shape[1:3])}")
                 call("vae2_bn_reduce_finalize", ptr(stats), rows, cout, ptr(sums), count,
                      ptr(gamma), ptr(beta), *stat_ptrs, spec.momentum, spec.eps, ptr(save), s)
             else:  # SyncBN: exchange the double sums between the reduction and finalize
@@ -671,25 +705,18 @@ class _ConvBN(torch.autograd.Function):
                 call("vae2_bn_finalize", ptr(sums), count, ptr(gamma), ptr(beta), *stat_ptrs,
                      spec.momentum, spec.eps, cout, ptr(save), s)
         else:
-            r = _conv_fwd(x, weight, bias, spec)
             save = _empty((4 * cout,), x)
             call("vae2_bn_eval_coeffs", ptr(gamma), ptr(beta), ptr(bn.running_mean),
                  ptr(bn.running_var), spec.eps, cout, ptr(save), s)
-        y = new_act((n, oh, ow, cout), x)
+        y = new_act(tuple(r.shape), x)
         rp, ra = act_of(r)
         yp, ya = act_of(y)
-        if residual is not None:
-            resp, resa = act_of(residual)
-        else:
-            resp, resa = None, ya
+        resp, resa = act_of(residual) if residual is not None else (None, ya)
         if prof.active():  # read r (+ residual), write y
             prof.note(0, 4.0 * r.numel() * (3 if residual is not None else 2))
         call("vae2_bn_apply", rp, ctypes.byref(ra), ptr(save), resp, ctypes.byref(resa), yp,
              ctypes.byref(ya), int(spec.relu), s)
-        ctx.spec = spec
-        ctx.count = count
-        ctx.group = group
-        ctx.has_res = residual is not None
+        ctx.spec, ctx.count, ctx.group, ctx.has_res = spec, count, group, residual is not None
         ctx.params = (weight, bias, gamma, beta)
         ctx.save_for_backward(x, r, y, save)
         return y
@@ -698,62 +725,49 @@ class _ConvBN(torch.autograd.Function):
     def backward(ctx, dy):
         if not ctx.spec.training:
             raise RuntimeError("backward through an eval-mode BatchNorm is not supported")
-        lib = _lib.load()
         s = stream_ptr()
         x, r, y, save = ctx.saved_tensors
-        weight, bias, gamma, beta = ctx.params
-        spec = ctx.spec
-        dy = as_act(dy)
-        cout = r.shape[3]
-        dyp, dya = act_of(dy)
-        rp, ra = act_of(r)
-        yp, ya = act_of(y)
+        (weight, bias, gamma, beta), spec = ctx.params, ctx.spec
+        need = _In(*ctx.needs_input_grad[:len(_In._fields)])
+        dy, cout = as_act(dy), r.shape[3]
+        (dyp, dya), (rp, ra), (yp, ya) = act_of(dy), act_of(r), act_of(y)
         if not ctx.has_res:
             yp = None  # the kernels recompute the ReLU mask from r (no read of y)
-        rows = lib.vae2_bn_partial_rows(ctypes.byref(ra))
+        rows = _lib.load().vae2_bn_partial_rows(ctypes.byref(ra))
         part = _empty((2 * rows * cout,), r)
         if prof.active():  # read dy, r (+ y)
             prof.note(0, 4.0 * r.numel() * (3 if yp is not None else 2))
         call("vae2_bn_relu_bwd_reduce", dyp, ctypes.byref(dya), yp, ctypes.byref(ya), rp,
              ctypes.byref(ra), ptr(save), int(spec.relu), ptr(part), s)
         lsums = _empty((2 * cout,), r, torch.float64)
-        gsink, gret = _grad_sink(gamma, ctx.needs_input_grad[3])
-        bsink, bret = _grad_sink(beta, ctx.needs_input_grad[4])
+        gsink, gret = _grad_sink(gamma, need.gamma)
+        bsink, bret = _grad_sink(beta, need.beta)
         call("vae2_bn_bwd_reduce_param_grads", ptr(part), rows, cout, ptr(lsums), ptr(gsink),
              ptr(bsink), s)
         gsums, _ = _all_reduce_sums(lsums, ctx.count, ctx.group)
         dr = new_act(tuple(r.shape), r)
         drp, dra = act_of(dr)
-        dres = None
-        link = spec.res_link
-        if ctx.has_res and ctx.needs_input_grad[5]:
-            dres = new_act(tuple(r.shape), r)
-            dresp, dresa = act_of(dres)
-        else:
-            dresp, dresa = None, dra
+        dres = new_act(tuple(r.shape), r) if ctx.has_res and need.residual else None
+        dresp, dresa = act_of(dres) if dres is not None else (None, dra)
         if prof.active():  # read dy, r (+ y); write dr (+ dres)
             prof.note(0, 4.0 * r.numel() * (3 + (1 if yp is not None else 0) +
                                              (1 if dres is not None else 0)))
         call("vae2_bn_relu_bwd_apply", dyp, ctypes.byref(dya), yp, ctypes.byref(ya), rp,
              ctypes.byref(ra), ptr(save), ptr(gamma), ptr(gsums), ctx.count, int(spec.relu), drp,
              ctypes.byref(dra), dresp, ctypes.byref(dresa), s)
-        if dres is not None and link is not None:
-            if link.buf is None:
-                link.buf = dres
-            else:  # (not reached by the blocks: conv1's backward runs after this one)
-                link.buf.add_(dres)
-            dres = link.finish()
-        dx, wret, bret_conv = _conv_bwd(x, weight, bias, dr, spec, ctx.needs_input_grad[0],
-                                        ctx.needs_input_grad[1], ctx.needs_input_grad[2])
-        return dx, wret, bret_conv, gret, bret, dres, None
+        if dres is not None and spec.res_link is not None:
+            dres = spec.res_link.hand_over(dres)  # (an add_: not reached by the blocks)
+        dx, wret, bret_conv = _conv_bwd(x, weight, bias, dr, spec, need.x, need.weight, need.bias)
+        return (*_In(dx, wret, bret_conv, gret, bret, dres), None)
 
 
 def conv_bn(x, conv, bn, relu, residual=None, x_link=None, res_link=None, bn_part=None):
     """relu?(bn(conv(x)) + residual) with training-mode (or eval-mode) BatchNorm.
     x_link / res_link: GradLink shared with the other consumer(s) of x / residual.
     bn_part: the PartBN of the layer that produced x (its partials from this conv's data
-    gradient).  Training mode goes through the multi-layer path (one layer); eval mode, and
-    residual views the multi-layer kernels cannot take, through _ConvBN."""
+    gradient; claimed here).  Training mode goes through the multi-layer path (one layer);
+    eval mode, and residual views the multi-layer kernels cannot take, through _ConvBN."""
+    _claim((bn_part,))
     spec = ConvSpec(conv, bn, relu)
     spec.x_link, spec.res_link = x_link, res_link
     spec.bn_part = bn_part if PART_BN else None
@@ -769,18 +783,10 @@ def _bn_quad_ok(t):
     return p_.value % 16 == 0 and a.ps % 4 == 0 and a.c <= 1024
 
 
-_COUNTS = {}
-
-
-def _counts_dev(counts, like):
-    """Device copy of per-layer element counts (cached: the SyncBN exchange appends
-    them to the statistics so the global count is the sum of the real local counts)."""
-    key = (tuple(counts), like.device)
-    t = _COUNTS.get(key)
-    if t is None:
-        t = torch.tensor(counts, dtype=torch.float64).to(like.device)
-        _COUNTS[key] = t
-    return t
+@functools.lru_cache(maxsize=None)
+def _counts_dev(counts, device):
+    """Device copy (cached) of a level's per-layer element counts, for the SyncBN exchange."""
+    return torch.tensor(counts, dtype=torch.float64).to(device)
 
 
 LEVEL_LANES = 0  # concurrent lanes per depth level inside a graph capture (0/1: off; measured slower, DESIGN.md)
@@ -851,290 +857,291 @@ class _Lanes:
                 st.wait_stream(self.parent)
 
 
+class _Layer:
+    """One conv -> BN layer of a _ConvBNMulti level: its autograd inputs (_In's names), its spec
+    and what the passes derive (per-layer record).  stats / rows: the partials a BnFin
+    reduces, (sum x, sum x^2) from the conv's epilogue in the forward, (sum g, sum g*xhat) in the
+    backward; r: the pre-BN conv output; y: the output (r itself where it is never stored); dy /
+    dr / dres: the gradients of y / r / the residual; gret / bret: autograd's for gamma / beta."""
+    __slots__ = _In._fields + ("spec", "has_res", "cout", "count", "rows", "stats", "r", "save",
+                               "y", "mask", "dy", "dr", "dres", "acc", "gret", "bret")
+
+    def __init__(self, spec, ins):
+        self.cout = self.count = self.rows = self.stats = self.r = self.save = self.y = None
+        self.mask = self.dy = self.dr = self.dres = self.acc = self.gret = self.bret = None
+        self.spec, self.has_res = spec, ins.residual is not None
+        self.x, self.weight, self.bias, self.gamma, self.beta, self.residual = ins
+
+    def conv(self, group=None, sp=None, stats=True):
+        """The layer's conv into self.r (+ its BN statistics partials unless stats is False)."""
+        x, spec = self.x, self.spec
+        n, h, w, _ = x.shape
+        oh, ow = spec.out_hw(h, w)
+        cout, self.count = self.weight.shape[0], float(n * oh * ow)
+        self.cout = cout
+        if stats:
+            xp, xa = act_of(x)
+            self.rows = _lib.load().vae2_conv2d_fwd_stats_rows(
+                xp, ctypes.byref(xa), ctypes.byref(Act(n, oh, ow, cout, cout)), spec.k,
+                spec.stride, spec.pad)
+            self.stats = _empty((2 * self.rows * cout,), x)
+        self.r = _conv_fwd(x, self.weight, self.bias, spec, self.stats, group, sp)
+        return self.r
+
+
+def _sums_layout(layers, group):
+    """The level's fp64 buffer [2*C_0 | 2*C_1 | ... | n counts] and per layer (sums_ptr,
+    count_ptr) into it; counts filled (else count_ptr null) under SyncBN, which exchanges them."""
+    n, tot = len(layers), 2 * sum(L.cout for L in layers)
+    buf = _empty((tot + n,), layers[0].r, torch.float64)
+    if group is not None:
+        buf[tot:].copy_(_counts_dev(tuple(L.count for L in layers), buf.device))
+    base, off, ptrs = buf.data_ptr(), 0, []
+    for i, L in enumerate(layers):
+        ptrs.append((base + 8 * off, base + 8 * (tot + i) if group is not None else None))
+        off += 2 * L.cout
+    return buf, ptrs
+
+
+def _bn_fin(L, sums_p, countp=None, gamma=None, beta=None, running=(None, None, None),
+            momentum=0.0, eps=0.0, save=None, dgamma=None, dbeta=None):
+    """BnFin of layer L: its partials (L.stats, L.rows) reduced into the sums at sums_p."""
+    return _lib.BnFin(L.stats.data_ptr(), L.rows, L.cout, sums_p, countp, L.count, ptr(gamma),
+                      ptr(beta), *running, momentum, eps, ptr(save), ptr(dgamma), ptr(dbeta))
+
+
+def _ride_shortcut(layer, S, rsums_p=None):
+    """BnLayer `layer`'s residual is shortcut layer S's BatchNorm output (ResBN), formed from S.r;
+    in the backward (rsums_p: S's sums) its kernels also write S's partials and S.dr."""
+    layer.rx, layer.rxd, layer.rsave = S.r.data_ptr(), act_of(S.r)[1], S.save.data_ptr()
+    if rsums_p is not None:
+        layer.rgamma, layer.rpartials, layer.rsums = ptr(S.gamma), S.stats.data_ptr(), rsums_p
+        layer.rdx, layer.rdxd = S.dr.data_ptr(), act_of(S.dr)[1]
+
+
+def _bn_note(kind, Ls, passes):
+    """Profiler note of a BN launch over layers Ls: passes(L) tensors of L.r's size moved."""
+    if prof.active():
+        prof.note(0, sum(4.0 * L.r.numel() * passes(L) for L in Ls),
+                  f"{kind} " + " + ".join("%d@%dx%d" % (L.r.shape[3], *L.r.shape[1:3]) for L in Ls))
+
+
+def _level_convs(layers):
+    """Forward step 1, the level's convs (+ statistics partials): one vae2_conv2d_multi call (a
+    LazyBN input: vae2_conv2d_fwd_bnin at once), or vae2_conv2d_fwd per layer on joined lanes."""
+    lanes = _Lanes([L.spec for L in layers])
+    cg = None if lanes.on else ConvGroup()
+    for i, L in enumerate(layers):
+        L.conv(cg, lanes.ptr(i))
+        L.save = _empty((4 * L.cout,), L.x)
+    if cg is not None:
+        cg.flush()  # the level's convs: direct-3x3 layers share launches
+    lanes.join()
+
+
+def _level_stats(layers, group, s):
+    """Forward step 2, batch statistics / running stats / L.save: vae2_bn_multi_reduce mode 0; or
+    (SyncBN) mode 2, one exchange of the sums and counts, vae2_bn_multi_finalize.  Returns buf."""
+    n = len(layers)
+    buf, sp = _sums_layout(layers, group)
+    world = dist.get_world_size(group) if group is not None else 1
+    arr = (_lib.BnFin * n)()
+    for i, L in enumerate(layers):
+        if L.count * world <= 1:
+            raise ValueError("Expected more than 1 value per channel when training, "
+                             f"got input size {(L.count, L.cout)}")
+        arr[i] = _bn_fin(L, *sp[i], L.gamma, L.beta, _running_ptrs(L.spec.bn), L.spec.momentum,
+                         L.spec.eps, L.save)
+    if group is None:
+        call("vae2_bn_multi_reduce", n, arr, 0, s)
+    else:  # SyncBN: one exchange of every layer's (sum x, sum x^2) and count
+        call("vae2_bn_multi_reduce", n, arr, 2, s)
+        from . import dist as vdist
+        vdist.syncbn_all_reduce_(buf, group=group)
+        call("vae2_bn_multi_finalize", n, arr, s)
+    return buf
+
+
+def _level_apply(layers, s):
+    """Forward step 3: vae2_bn_multi_apply for the layers whose output is stored (L.y, + the ReLU
+    byte mask); LazyBN / PartBN layers publish to their marker, a LazyBN's / ResBN's y is r."""
+    lay = []
+    for L in layers:
+        spec, lz, res = L.spec, L.spec.bn_out, L.residual
+        if isinstance(lz, PartBN):  # y stored as usual; the consumer's dgrad writes the partials
+            lz.publish(L.save, spec.relu, L.r if res is None and spec.res_bn is None else None)
+        elif lz is not None:
+            if not isinstance(lz, ResBN):
+                lz.publish(L.save, spec.relu)
+            L.y = L.r
+            continue
+        L.y = new_act(tuple(L.r.shape), L.r)
+        layer = _bn_layer(L.r, res, L.y, None, None, L.save, None, None, None, None, 0.0,
+                          spec.relu)
+        if MASK_BYTES and spec.relu and (res is not None or spec.res_bn is not None):
+            # the backward's ReLU mask (not recomputable from r): 1 byte per channel quad
+            _, ya_ = act_of(L.y)
+            L.mask = torch.empty((ya_.n * ya_.h * ya_.w * ((ya_.c + 3) // 4),),
+                                 dtype=torch.uint8, device=L.y.device)
+            layer.mask = L.mask.data_ptr()
+        if spec.res_bn is not None:
+            _ride_shortcut(layer, layers[spec.res_bn])
+        lay.append(layer)
+    if lay:
+        _bn_note("bn apply", [L for L in layers if L.spec.bn_out is None],
+                 lambda L: 3 if L.has_res or L.spec.res_bn is not None else 2)
+        call("vae2_bn_multi_apply", len(lay), (_lib.BnLayer * len(lay))(*lay), s)
+
+
+def _resbn_buffers(layers):
+    """Backward step 1 (no launch): the buffers a shortcut BN's (ResBN) consumer writes for it
+    (partials, input gradient), first, so that the consumer's descriptor can point at them."""
+    for L in layers:
+        if isinstance(L.spec.bn_out, ResBN):
+            L.rows = _lib.load().vae2_bn_partial_rows(ctypes.byref(act_of(L.r)[1]))
+            L.stats = _empty((2 * L.rows * L.cout,), L.r)
+            L.dr = new_act(tuple(L.r.shape), L.r)
+
+
+def _bn_bwd_descs(ctx, layers, dys, sp):
+    """Backward step 2: the BN backward's BnLayer / BnFin descriptors and their buffers (on the
+    records).  Returns (lay, fins, red, act): act = layers with BN passes of their own (not
+    ResBN), red = those running the reduce pass too.  Launches vae2_copy_act for a misaligned dy."""
+    n = len(layers)
+    lay, fins, red, act = (_lib.BnLayer * n)(), (_lib.BnFin * n)(), [], []
+    for i, L in enumerate(layers):
+        spec, r, lz, need = L.spec, L.r, L.spec.bn_out, _layer_needs(ctx.needs_input_grad, i)
+        own = not isinstance(lz, ResBN)
+        if own:
+            act.append(i)
+            dy = as_act(dys[i]) if dys[i] is not None else torch.zeros_like(L.y)
+            L.dy = dy if _bn_quad_ok(dy) else _aligned_copy(dy)  # (e.g. a channel slice)
+            L.stats, L.rows = (lz.take_partials() if lz is not None and dys[i] is not None
+                               else (None, 0))
+            if L.stats is None:  # none from the consumer's data gradient: own reduce pass
+                L.rows = _lib.load().vae2_bn_partial_rows(ctypes.byref(act_of(r)[1]))
+                L.stats = _empty((2 * L.rows * L.cout,), r)
+                red.append(i)
+            L.dr, L.acc, link = new_act(tuple(r.shape), r), 0, spec.res_link
+            if L.has_res and need.residual:
+                if (link is not None and link.buf is not None and
+                        tuple(link.buf.shape) == tuple(r.shape) and _bn_quad_ok(link.buf)):
+                    L.dres, L.acc = link.buf, 1  # summed onto the other consumer's in-kernel
+                else:
+                    L.dres = new_act(tuple(r.shape), r)
+        gsink, L.gret = _grad_sink(L.gamma, need.gamma)
+        bsink, L.bret = _grad_sink(L.beta, need.beta)
+        fins[i] = _bn_fin(L, sp[i][0], dgamma=gsink, dbeta=bsink)
+        if own:
+            y = L.y if (L.has_res or spec.res_bn is not None) and L.mask is None else None
+            layer = _bn_layer(r, y, L.dr, L.dy, L.dres, L.save, L.gamma, L.stats, *sp[i],
+                              L.count, spec.relu, L.acc)
+            if L.mask is not None:
+                layer.mask = L.mask.data_ptr()
+            if spec.res_bn is not None:  # the shortcut BN's passes ride on this layer's
+                _ride_shortcut(layer, layers[spec.res_bn], sp[spec.res_bn][0])
+            lay[i] = layer
+    return lay, fins, red, act
+
+
+def _bn_bwd_launch(layers, descs, buf, group, s):
+    """Backward step 3: vae2_bn_multi_bwd_reduce (`red`), vae2_bn_multi_reduce mode 1 (all: sums,
+    dgamma / dbeta; + the SyncBN exchange), vae2_bn_multi_bwd_apply (`act`: dr, dres)."""
+    lay, fins, red, act = descs
+    if red:
+        _bn_note("bn bwd reduce", [layers[i] for i in red],
+                 lambda L: 2 + _y_reads(L) + (1 if L.spec.res_bn is not None else 0))
+        call("vae2_bn_multi_bwd_reduce", len(red),
+             (_lib.BnLayer * len(red))(*[lay[i] for i in red]), s)
+    call("vae2_bn_multi_reduce", len(layers), fins, 1, s)  # local sums + dgamma / dbeta
+    if group is not None:  # SyncBN: global (sum g, sum g*xhat) for the input gradients
+        from . import dist as vdist
+        vdist.syncbn_all_reduce_(buf, group=group)
+    _bn_note("bn bwd apply", [layers[i] for i in act],
+             lambda L: (3 + _y_reads(L) + (1 if L.dres is not None else 0) +
+                        (2 if L.spec.res_bn is not None else 0)))
+    call("vae2_bn_multi_bwd_apply", len(act), (_lib.BnLayer * len(act))(*[lay[i] for i in act]),
+         s)
+
+
+def _level_conv_grads(ctx, layers):
+    """Backward steps 4 and 5, per layer in turn (the order matters to a shared GradLink): the
+    residual gradient's hand_over to its res_link, then _conv_bwd (data gradients on one
+    ConvGroup or on lanes; the weight-gradient reductions in one launch, wgrad_batch)."""
+    grads, hold = [], []
+    lanes = _Lanes([L.spec for L in layers], LEVEL_LANES_BWD)
+    cg = None if lanes.on else ConvGroup()
+
+    def settle(buf):  # before an add_ onto buf: a queued job or a lane may still write it
+        if cg is not None and cg.pending(buf):
+            cg.flush()
+        lanes.sync()
+
+    with wgrad_batch():
+        for i, L in enumerate(layers):
+            need, dres = _layer_needs(ctx.needs_input_grad, i), L.dres
+            if dres is not None and L.spec.res_link is not None:
+                dres = L.spec.res_link.hand_over(dres, settle)
+            dx, wret, bret_conv = _conv_bwd(L.x, L.weight, L.bias, L.dr, L.spec, need.x,
+                                            need.weight, need.bias, group=cg, sp=lanes.ptr(i),
+                                            hold=hold)
+            grads.append(_In(dx, wret, bret_conv, L.gret, L.bret, dres))
+        if cg is not None:
+            cg.flush()
+        lanes.join()
+    del hold  # (after the join: the lanes' workspaces return to the parent's pool)
+    return _level_grads(grads)
+
+
 class _ConvBNMulti(torch.autograd.Function):
     """n independent conv -> BatchNorm(train) [-> +residual] [-> ReLU] layers (one HRNet
     depth level): the convs launch per layer, every BatchNorm step is one launch for all
     n layers (vae2_bn_multi_*), and with SyncBN one exchange carries all n layers'
-    statistics and element counts.  flat = (x, weight, bias, gamma, beta, residual) per
-    layer."""
+    statistics and element counts.  flat = _In's fields per layer -> a list of _Layer records."""
 
     @staticmethod
     def forward(ctx, specs, *flat):
-        lib = _lib.load()
         s = stream_ptr()
-        n = len(specs)
-        L = [flat[6 * i:6 * i + 6] for i in range(n)]
-        group = _bn_group()
-        rs, saves, fins, counts, cs = [], [], [], [], []
-        lanes = _Lanes(specs)
-        cg = None if lanes.on else ConvGroup()
-        for li, ((x, weight, bias, gamma, beta, residual), spec) in enumerate(zip(L, specs)):
-            nn_, h, w, _ = x.shape
-            oh, ow = spec.out_hw(h, w)
-            cout = weight.shape[0]
-            xp, xa = act_of(x)
-            rows = lib.vae2_conv2d_fwd_stats_rows(xp, ctypes.byref(xa),
-                                                  ctypes.byref(Act(nn_, oh, ow, cout, cout)),
-                                                  spec.k, spec.stride, spec.pad)
-            stats = _empty((2 * rows * cout,), x)
-            rs.append(_conv_fwd_queued(cg, x, weight, bias, spec, stats, lanes.ptr(li)))
-            saves.append(_empty((4 * cout,), x))
-            counts.append(float(nn_ * oh * ow))
-            cs.append(cout)
-            fins.append((stats, rows))
-        if cg is not None:
-            cg.flush()  # the level's convs: direct-3x3 layers share launches
-        lanes.join()
-        tot = 2 * sum(cs)
-        buf = _empty((tot + n,), rs[0], torch.float64)
-        world = 1
-        if group is not None:
-            buf[tot:].copy_(_counts_dev(counts, buf))
-            world = dist.get_world_size(group)
-        arr = (_lib.BnFin * n)()
-        off = 0
-        for i, ((stats, rows), spec, c) in enumerate(zip(fins, specs, cs)):
-            bn = spec.bn
-            gamma, beta = L[i][3], L[i][4]
-            if counts[i] * world <= 1:
-                raise ValueError("Expected more than 1 value per channel when training, "
-                                 f"got input size {(counts[i], c)}")
-            track = bn.track_running_stats and bn.running_mean is not None
-            arr[i] = _lib.BnFin(
-                stats.data_ptr(), rows, c, buf.data_ptr() + 8 * off,
-                buf.data_ptr() + 8 * (tot + i) if group is not None else None, counts[i],
-                _p(gamma), _p(beta), _p(bn.running_mean) if track else None,
-                _p(bn.running_var) if track else None,
-                _p(bn.num_batches_tracked) if track else None, spec.momentum, spec.eps,
-                saves[i].data_ptr(), None, None)
-            off += 2 * c
-        if group is None:
-            call("vae2_bn_multi_reduce", n, arr, 0, s)
-        else:  # SyncBN: one exchange of every layer's (sum x, sum x^2) and count
-            call("vae2_bn_multi_reduce", n, arr, 2, s)
-            from . import dist as vdist
-            vdist.syncbn_all_reduce_(buf, group=group)
-            call("vae2_bn_multi_finalize", n, arr, s)
-        ys, lay = [], []
-        masks = [None] * n
-        for i, (r, save, spec) in enumerate(zip(rs, saves, specs)):
-            lz = spec.bn_out
-            if isinstance(lz, ResBN):  # added by its consumer's apply: r stands in for y
-                ys.append(r)
-                continue
-            if isinstance(lz, PartBN):  # y stored as usual; the consumer's data gradient
-                ok = L[i][5] is None and spec.res_bn is None  # will write the partials
-                lz.save, lz.relu, lz.part, lz.rows = save, spec.relu, None, 0
-                lz.r = r if ok else None
-                lz = None
-            if lz is not None:  # normalised by the consumer conv: r stands in for y
-                lz.save, lz.relu, lz.part, lz.rows = save, spec.relu, None, 0
-                ys.append(r)
-                continue
-            y = new_act(tuple(r.shape), r)
-            ys.append(y)
-            res = L[i][5]
-            layer = _bn_layer(r, res, y, None, None, save, None, None, None, None, 0.0,
-                              spec.relu)
-            if MASK_BYTES and spec.relu and (res is not None or spec.res_bn is not None):
-                # the backward's ReLU mask (it cannot be recomputed from r): 1 byte per
-                # channel quad instead of re-reading y twice
-                _, ya_ = act_of(y)
-                mk = torch.empty((ya_.n * ya_.h * ya_.w * ((ya_.c + 3) // 4),),
-                                 dtype=torch.uint8, device=y.device)
-                layer.mask = mk.data_ptr()
-                masks[i] = mk
-            if spec.res_bn is not None:
-                j = spec.res_bn
-                layer.rx, layer.rxd = rs[j].data_ptr(), act_of(rs[j])[1]
-                layer.rsave = saves[j].data_ptr()
-            lay.append(layer)
-        if lay:
-            if prof.active():
-                prof.note(0, sum(4.0 * r.numel() * (3 if L[i][5] is not None or
-                                                    specs[i].res_bn is not None else 2)
-                                 for i, r in enumerate(rs) if specs[i].bn_out is None),
-                          _bn_label("bn apply", [rs[i] for i in range(n)
-                                                 if specs[i].bn_out is None]))
-            call("vae2_bn_multi_apply", len(lay), (_lib.BnLayer * len(lay))(*lay), s)
-        ctx.specs = specs
-        ctx.masks = masks
-        ctx.counts = counts
-        ctx.group = group
-        ctx.has_res = [l_[5] is not None for l_ in L]
-        ctx.params = [l_[1:5] for l_ in L]
-        ctx.save_for_backward(*[l_[0] for l_ in L], *rs, *ys, *saves)
-        return tuple(ys)
+        ctx.group = _bn_group()
+        ins = map(_In._make, zip(*[iter(flat)] * len(_In._fields)))
+        layers = [_Layer(spec, i_) for spec, i_ in zip(specs, ins)]
+        _level_convs(layers)
+        sums = _level_stats(layers, ctx.group, s)  # (stays allocated to the end of the forward)
+        _level_apply(layers, s)
+        ys = tuple(L.y for L in layers)
+        ctx.save_for_backward(*[t for L in layers for t in (L.x, L.r, L.y, L.save)])
+        for L in layers:  # the context keeps the records, these tensors go through autograd
+            L.x = L.r = L.y = L.save = L.residual = L.stats = None
+        ctx.layers = layers
+        del sums
+        return ys
 
     @staticmethod
     def backward(ctx, *dys):
         s = stream_ptr()
-        specs = ctx.specs
-        n = len(specs)
-        saved = ctx.saved_tensors
-        xs, rs, ys, saves = (saved[k * n:(k + 1) * n] for k in range(4))
-        need = ctx.needs_input_grad
-        cs = [int(r.shape[3]) for r in rs]
-        tot = 2 * sum(cs)
-        buf = _empty((tot + n,), rs[0], torch.float64)
-        group = ctx.group
-        if group is not None:
-            buf[tot:].copy_(_counts_dev(ctx.counts, buf))
-        lay = (_lib.BnLayer * n)()
-        fins = (_lib.BnFin * n)()
-        keep, drs, dress, red = [], [], [], []
-        off = 0
-        lib = _lib.load()
-        # a shortcut BN (ResBN) gets its partials / input gradient from its consumer's
-        # kernels: its buffers first, so the consumer's layer can point at them
-        resbuf, o_ = {}, 0
-        for i in range(n):
-            if isinstance(specs[i].bn_out, ResBN):
-                _, ra = act_of(rs[i])
-                rows = lib.vae2_bn_partial_rows(ctypes.byref(ra))
-                resbuf[i] = (_empty((2 * rows * cs[i],), rs[i]), rows,
-                             new_act(tuple(rs[i].shape), rs[i]), buf.data_ptr() + 8 * o_)
-            o_ += 2 * cs[i]
-        act = []  # layers with BN passes of their own (not ResBN)
-        for i in range(n):
-            r, y, save, spec = rs[i], ys[i], saves[i], specs[i]
-            if i in resbuf:
-                part, rows, dr, sums_p = resbuf[i]
-                gamma, beta = ctx.params[i][2], ctx.params[i][3]
-                gsink, gret = _grad_sink(gamma, need[1 + 6 * i + 3])
-                bsink, bret = _grad_sink(beta, need[1 + 6 * i + 4])
-                fins[i] = _lib.BnFin(part.data_ptr(), rows, cs[i], sums_p, None, ctx.counts[i],
-                                     None, None, None, None, None, 0.0, 0.0, None, _p(gsink),
-                                     _p(bsink))
-                keep.append((part,))
-                drs.append(dr)
-                dress.append((None, gret, bret))
-                off += 2 * cs[i]
-                continue
-            act.append(i)
-            dy = dys[i]
-            dy = as_act(dy) if dy is not None else torch.zeros_like(y)
-            if not _bn_quad_ok(dy):  # e.g. a channel slice of a concatenation's gradient
-                dy = _aligned_copy(dy)
-            lz = spec.bn_out
-            pre = lz is not None and lz.part is not None and dys[i] is not None
-            if pre:  # partials from the consumer's data-gradient epilogue
-                part, rows = lz.part, lz.rows
-                lz.part = None
-            else:
-                _, ra = act_of(r)
-                rows = lib.vae2_bn_partial_rows(ctypes.byref(ra))
-                part = _empty((2 * rows * cs[i],), r)
-                red.append(i)
-            dr = new_act(tuple(r.shape), r)
-            dres, acc = None, 0
-            if ctx.has_res[i] and need[1 + 6 * i + 5]:
-                link = spec.res_link
-                if (link is not None and link.buf is not None and
-                        tuple(link.buf.shape) == tuple(r.shape) and _bn_quad_ok(link.buf)):
-                    dres, acc = link.buf, 1  # summed onto the other consumer's gradient in-kernel
-                else:
-                    dres = new_act(tuple(r.shape), r)
-            gamma, beta = ctx.params[i][2], ctx.params[i][3]
-            gsink, gret = _grad_sink(gamma, need[1 + 6 * i + 3])
-            bsink, bret = _grad_sink(beta, need[1 + 6 * i + 4])
-            sums_p = buf.data_ptr() + 8 * off
-            countp = buf.data_ptr() + 8 * (tot + i) if group is not None else None
-            mk = ctx.masks[i]
-            lay[i] = _bn_layer(r, y if (ctx.has_res[i] or spec.res_bn is not None) and mk is None
-                               else None, dr, dy, dres, save, gamma, part, sums_p, countp,
-                               ctx.counts[i], spec.relu, acc)
-            if mk is not None:
-                lay[i].mask = mk.data_ptr()
-            if spec.res_bn is not None:  # the shortcut BN's passes ride on this layer's
-                j = spec.res_bn
-                rpart, _, rdr, rsums_p = resbuf[j]
-                lay[i].rx, lay[i].rxd = rs[j].data_ptr(), act_of(rs[j])[1]
-                lay[i].rsave = saves[j].data_ptr()
-                lay[i].rgamma = _p(ctx.params[j][2])
-                lay[i].rpartials, lay[i].rsums = rpart.data_ptr(), rsums_p
-                lay[i].rdx, lay[i].rdxd = rdr.data_ptr(), act_of(rdr)[1]
-            fins[i] = _lib.BnFin(part.data_ptr(), rows, cs[i], sums_p, None, ctx.counts[i],
-                                 None, None, None, None, None, 0.0, 0.0, None, _p(gsink),
-                                 _p(bsink))
-            keep.append((dy, part))
-            drs.append(dr)
-            dress.append((dres, gret, bret))
-            off += 2 * cs[i]
-        if red:
-            if prof.active():
-                prof.note(0, sum(4.0 * rs[i].numel() * (2 + _y_reads(ctx, i) +
-                                                        (1 if specs[i].res_bn is not None else 0))
-                                 for i in red), _bn_label("bn bwd reduce", [rs[i] for i in red]))
-            call("vae2_bn_multi_bwd_reduce", len(red), (_lib.BnLayer * len(red))(*[lay[i] for i in red]),
-                 s)
-        call("vae2_bn_multi_reduce", n, fins, 1, s)  # local sums + dgamma / dbeta
-        if group is not None:  # SyncBN: global (sum g, sum g*xhat) for the input gradients
-            from . import dist as vdist
-            vdist.syncbn_all_reduce_(buf, group=group)
-        if prof.active():
-            prof.note(0, sum(4.0 * rs[i].numel() * (3 + _y_reads(ctx, i) +
-                                                    (1 if dress[i][0] is not None else 0) +
-                                                    (2 if specs[i].res_bn is not None else 0))
-                             for i in act), _bn_label("bn bwd apply", [rs[i] for i in act]))
-        call("vae2_bn_multi_bwd_apply", len(act), (_lib.BnLayer * len(act))(*[lay[i] for i in act]),
-             s)
-        grads = [None]
-        lanes = _Lanes(specs, LEVEL_LANES_BWD)
-        # the level's data gradients: direct-3x3 layers share launches (one stream), or the
-        # layers run on concurrent lanes (graph capture)
-        cg = None if lanes.on else ConvGroup()
-        hold = []
-        with wgrad_batch():  # the level's weight-gradient reductions in one launch
-            for i in range(n):
-                spec = specs[i]
-                x = xs[i]
-                weight, bias = ctx.params[i][0], ctx.params[i][1]
-                dres, gret, bret = dress[i]
-                link = spec.res_link
-                if dres is not None and link is not None:
-                    if link.buf is None:
-                        link.buf = dres
-                    elif link.buf is not dres:  # (dres is link.buf: summed in the BN kernel)
-                        if cg is not None and cg.pending(link.buf):
-                            cg.flush()
-                        if lanes.on:  # a lane may still be writing it
-                            lanes.sync()
-                        link.buf.add_(dres)
-                    dres = link.finish()
-                dx, wret, bret_conv = _conv_bwd(x, weight, bias, drs[i], spec, need[1 + 6 * i],
-                                                need[1 + 6 * i + 1], need[1 + 6 * i + 2],
-                                                group=cg, sp=lanes.ptr(i), hold=hold)
-                grads += [dx, wret, bret_conv, gret, bret, dres]
-            if cg is not None:
-                cg.flush()
-            lanes.join()
-        del hold  # (after the join: the lanes' workspaces return to the parent's pool)
-        return tuple(grads)
+        layers = ctx.layers
+        for L, saved in zip(layers, zip(*[iter(ctx.saved_tensors)] * 4)):
+            L.x, L.r, L.y, L.save = saved
+        buf, sp = _sums_layout(layers, ctx.group)
+        _resbn_buffers(layers)
+        descs = _bn_bwd_descs(ctx, layers, dys, sp)
+        _bn_bwd_launch(layers, descs, buf, ctx.group, s)
+        grads = _level_conv_grads(ctx, layers)
+        for L in layers:  # back to what the context keeps: nothing of this backward
+            L.x = L.r = L.y = L.save = L.stats = L.dy = L.dr = L.dres = L.gret = L.bret = None
+        return grads
 
 
-def _p(t):
-    return t.data_ptr() if t is not None else None
-
-
-def _y_reads(ctx, i):
-    """Bytes (in units of the layer's fp32 tensor) a backward pass reads for the ReLU mask:
-    y, its byte mask (1/16), or nothing (recomputed from r)."""
-    if ctx.masks[i] is not None:
+def _y_reads(L):
+    """Tensors of r's size a backward pass reads for the ReLU mask: y, its bytes (1/16), none."""
+    if L.mask is not None:
         return 1.0 / 16.0
-    return 1 if ctx.has_res[i] or ctx.specs[i].res_bn is not None else 0
-
-
-def _bn_label(kind, rs):
-    """Profiler row label of a multi-layer BN launch: its layers' C@HxW (N in the bytes)."""
-    return f"{kind} " + " + ".join(f"{int(r.shape[3])}@{int(r.shape[1])}x{int(r.shape[2])}"
-                                   for r in rs)
+    return 1 if L.has_res or L.spec.res_bn is not None else 0
 
 
 def _aligned_copy(t):
     out = new_act(tuple(t.shape), t)
-    tp, ta = act_of(t)
-    op, oa = act_of(out)
+    (tp, ta), (op, oa) = act_of(t), act_of(out)
     call("vae2_copy_act", tp, ctypes.byref(ta), op, ctypes.byref(oa), 0.0, stream_ptr())
     return out
 
@@ -1142,12 +1149,28 @@ def _aligned_copy(t):
 def _bn_layer(x, a, o, dy, dres, save, gamma, part, sums_p, countp, count, relu, dres_acc=0):
     def d(t):
         return act_of(t)[1] if t is not None else Act(0, 0, 0, 0, 0)
-    return _lib.BnLayer(_p(x), d(x), _p(a), d(a), _p(o), d(o), _p(dy), d(dy), _p(dres), d(dres),
-                        _p(save), _p(gamma), _p(part), sums_p, countp, float(count), int(relu),
-                        int(dres_acc))
+    return _lib.BnLayer(ptr(x), d(x), ptr(a), d(a), ptr(o), d(o), ptr(dy), d(dy), ptr(dres),
+                        d(dres), ptr(save), ptr(gamma), ptr(part), sums_p, countp, float(count),
+                        int(relu), int(dres_acc))
 
 
 BN_BATCH = True  # False: conv_bn_multi runs its layers one by one (A/B and parity tests)
+
+
+def _check_res_bns(res_bns, xs, convs, specs, residuals, bn_outs):
+    """conv_bn_multi's res_bns contract; marks each pair on its specs (res_bn, bn_out=ResBN())."""
+    for i, j in enumerate(res_bns):
+        if j is None:
+            continue
+        if (residuals[i] is not None or residuals[j] is not None or specs[j].relu or
+                res_bns[j] is not None or bn_outs[i] is not None or bn_outs[j] is not None):
+            raise ValueError("res_bns: the shortcut layer must be a plain conv + BN")
+        shp = [(xs[k].shape[0], *specs[k].out_hw(xs[k].shape[1], xs[k].shape[2]),
+                convs[k].out_channels) for k in (i, j)]
+        if shp[0] != shp[1]:
+            raise ValueError(f"res_bns: shortcut output {shp[1]} != layer output {shp[0]}")
+        specs[i].res_bn = j
+        specs[j].bn_out = ResBN()
 
 
 def conv_bn_multi(xs, convs, bns, relu, residuals=None, x_links=None, res_links=None,
@@ -1160,63 +1183,45 @@ def conv_bn_multi(xs, convs, bns, relu, residuals=None, x_links=None, res_links=
     that takes it lazily -- the returned tensor is then the pre-BN conv output, to be
     passed on with bn_ins[i] = that LazyBN to the consumer's conv_bn_multi call.  Where
     the batched path does not run, the entry is set to None (the output is stored).
-    A PartBN entry instead keeps the stored output and, passed on as the consumer's
-    bn_ins[i], makes the consumer's data gradient write layer i's backward partials.
+    A PartBN entry instead keeps the stored output and, as the consumer's bn_ins[i], makes its
+    data gradient write layer i's backward partials.  bn_ins markers are claimed here.
 
     res_bns[i] (an index j, or None): layer i's residual is layer j's BatchNorm output
     (layer j: no ReLU, no residual of its own, same output shape), added in layer i's
     apply and never stored (ResBN); layer j's entry of the returned list is then its
     pre-BN conv output, for no other use."""
     n = len(xs)
-    residuals = residuals if residuals is not None else [None] * n
-    x_links = x_links if x_links is not None else [None] * n
-    res_links = res_links if res_links is not None else [None] * n
+    nones = [None] * n
+    residuals, x_links, res_links = residuals or nones, x_links or nones, res_links or nones
+    outs_, ins_, res_bns = bn_outs or nones, bn_ins or nones, res_bns or nones
     relus = relu if isinstance(relu, (list, tuple)) else [relu] * n
+    _claim(ins_)
     specs = []
     for i in range(n):
         spec = ConvSpec(convs[i], bns[i], relus[i])
-        spec.x_link, spec.res_link = x_links[i], res_links[i]
-        if bn_outs is not None:
-            spec.bn_out = bn_outs[i]
-        if bn_ins is not None:
-            if isinstance(bn_ins[i], PartBN):  # stored input, partials from the dgrad
-                spec.bn_part = bn_ins[i] if PART_BN else None
-            else:
-                spec.bn_in = bn_ins[i]
+        spec.x_link, spec.res_link, spec.bn_out = x_links[i], res_links[i], outs_[i]
+        if isinstance(ins_[i], PartBN):  # stored input, partials from the dgrad
+            spec.bn_part = ins_[i] if PART_BN else None
+        else:
+            spec.bn_in = ins_[i]
         specs.append(spec)
-    if res_bns is not None:
-        for i, j in enumerate(res_bns):
-            if j is None:
-                continue
-            if (residuals[i] is not None or residuals[j] is not None or relus[j] or
-                    res_bns[j] is not None or (bn_outs is not None and
-                                               (bn_outs[i] is not None or bn_outs[j] is not None))):
-                raise ValueError("res_bns: the shortcut layer must be a plain conv + BN")
-            shp = [(xs[k].shape[0], *specs[k].out_hw(xs[k].shape[1], xs[k].shape[2]),
-                    convs[k].out_channels) for k in (i, j)]
-            if shp[0] != shp[1]:
-                raise ValueError(f"res_bns: shortcut output {shp[1]} != layer output {shp[0]}")
-            specs[i].res_bn = j
-            specs[j].bn_out = ResBN()
-    if (not BN_BATCH or not RES_BN and res_bns is not None and any(j is not None for j in res_bns)
+    _check_res_bns(res_bns, xs, convs, specs, residuals, outs_)
+    if (not BN_BATCH or not RES_BN and any(j is not None for j in res_bns)
             or not all(sp.training for sp in specs) or
             not all(r is None or _bn_quad_ok(r) for r in residuals)):
         if any(sp.bn_in is not None for sp in specs):
             raise RuntimeError("a LazyBN input needs the batched training path")
         if bn_outs is not None:
-            bn_outs[:] = [None] * n
+            bn_outs[:] = nones
         outs = [None] * n
-        order = [j for j in range(n) if res_bns is not None and j in res_bns]
+        order = [j for j in range(n) if j in res_bns]
         order += [i for i in range(n) if i not in order]
         for i in order:  # shortcut layers first: stored, then used as the residual
-            res = residuals[i]
-            if res_bns is not None and res_bns[i] is not None:
-                res = outs[res_bns[i]]
+            res = outs[res_bns[i]] if res_bns[i] is not None else residuals[i]
             outs[i] = conv_bn(xs[i], convs[i], bns[i], relus[i], res, x_links[i], res_links[i])
         return outs
-    flat = []
-    for i in range(n):
-        flat += [xs[i], convs[i].weight, convs[i].bias, bns[i].weight, bns[i].bias, residuals[i]]
+    flat = [t for i in range(n) for t in _In(xs[i], convs[i].weight, convs[i].bias,
+                                             bns[i].weight, bns[i].bias, residuals[i])]
     return list(_ConvBNMulti.apply(tuple(specs), *flat))
 
 
@@ -1224,8 +1229,7 @@ class _Conv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, spec):
         y = _conv_fwd(x, weight, bias, spec)
-        ctx.spec = spec
-        ctx.params = (weight, bias)
+        ctx.spec, ctx.params = spec, (weight, bias)
         ctx.save_for_backward(x)
         return y
 
@@ -1352,7 +1356,8 @@ def fuse_sum_relu(terms, out_hw, links=None, lazies=None):
     per term an ops.GradLink (or None) shared with the term's other consumers.  lazies:
     per term a LazyBN (or None): the term is that BatchNorm layer's pre-BN output, its
     normalised output (the fuse unit's BN, no ReLU) is formed here and never stored; the
-    gradient returned for the term is the one of that normalised output (LazyBN's rule)."""
+    gradient returned for the term is that normalised output's; the marker is claimed here."""
+    _claim(lazies)
     return _FuseSum.apply(tuple(out_hw), tuple(links) if links else None,
                           tuple(lazies) if lazies else None, *terms)
 
