@@ -922,6 +922,72 @@ def _multi_backward(lib, call, s, D, modes, rb, dacc, pad, r4k):
     return out
 
 
+def _multi_forward(call, s, D, modes, rb):
+    """vae2_bn_multi_apply on fresh buffers: y and the mask bytes per layer."""
+    from vae2 import _lib
+    lay = (_lib.BnLayer * len(D))()
+    keep = []
+    for i, d in enumerate(D):
+        has_rb = bool(rb) and i == RB_LAYER
+        res = d["res"] if modes[i] in ("mask", "y") and not has_rb else None
+        X, Y = S(with_nan_inf(d["x"]), "aligned"), S(torch.full(d["shape"], NAN), "aligned")
+        R = S(res, "aligned") if res is not None else None
+        RX = S(d["rx"], "aligned") if has_rb else None
+        MK = Guarded(torch.full((d["p"] * ((d["c"] + 3) // 4),), 0xFF, dtype=torch.uint8)) \
+            if modes[i] == "mask" else None
+        save, rsave = Guarded(d["save"]), Guarded(d["rsave"])
+        L = lay[i]
+        L.x, L.xd, L.o, L.od, L.save = X.ptr.value, X.act, Y.ptr.value, Y.act, save.addr
+        L.relu = int(modes[i] != "none")
+        if R:
+            L.a, L.ad = R.ptr.value, R.act
+        if RX:
+            L.rx, L.rxd, L.rsave = RX.ptr.value, RX.act, rsave.addr
+        if MK:
+            L.mask = MK.addr
+        keep.append((X, Y, R, RX, MK, save, rsave))
+    call("vae2_bn_multi_apply", len(D), lay, s)
+    torch.cuda.synchronize()
+    out = []
+    for X, Y, R, RX, MK, save, rsave in keep:
+        assert all(t is None or t.intact() for t in (X, Y, R, RX, MK, save, rsave))
+        out.append(dict(y=Y.read(), **({"mask": MK.read()} if MK else {})))
+    return out
+
+
+def test_multi_r4_matches_default_bits():
+    """Tune key 8 = 0 (and with it the fallback for extents of 2 GB or more) runs the same
+    arithmetic as the default buffer-resource kernels: every output of vae2_bn_multi_apply,
+    _bwd_reduce and _bwd_apply agrees bit for bit (y, part, rpart, dx, dres, rdx), and so do the
+    mask bytes' bits of the channels < C.  The bits of channels >= C in a partial quad's byte
+    come from lanes that see different coefficients in the two forms (0 / the next coefficient
+    row); they differ (C = 18 and 270 here), as they did before the bodies were shared, and no
+    kernel reads them (test_multi_apply_and_backward runs the backward on both paddings)."""
+    call, lib, ptr, s = abi()
+    modes = MODES["mix"]
+    D = [layer_data(c, shape, seed=i) for i, (c, shape) in enumerate(MULTI)]
+    runs = []
+    for r4k in (False, True):
+        with contextlib.ExitStack() as st:
+            st.enter_context(tune(lib, 19, 1024))
+            if r4k:
+                st.enter_context(tune(lib, 8, 0))
+            fwd = _multi_forward(call, s, D, modes, 1)
+            bwd = _multi_backward(lib, call, s, D, modes, 1, 1, 0, r4k)
+        runs.append([{**f, **b} for f, b in zip(fwd, bwd)])
+    seen = set()
+    for i, (a, b) in enumerate(zip(*runs)):
+        assert a.keys() == b.keys()
+        for key in a:
+            if key == "mask":  # one byte per (pixel, quad): the valid channels' bits
+                va, vb = (bn_ref.unpack_mask(t.view(D[i]["p"], -1), D[i]["c"]) for t in (a[key], b[key]))
+                assert torch.equal(va, vb), (i, key, MULTI[i])
+            else:
+                assert same_bits(a[key], b[key]), (i, key, MULTI[i])
+            seen.add(key)
+    assert seen == {"y", "mask", "part", "rpart", "dx", "dres", "rdx"}
+
+
 def test_rejected_multi_call_writes_nothing():
     """A layer of the second launch disagrees in shape: -22, and no layer's output is touched."""
     from vae2 import _lib

@@ -8,6 +8,12 @@
 // of per-channel fp32 sums per block (fixed pixel ranges), then one block per
 // channel sums the rows in double in a fixed tree order.  With SyncBN the double
 // sums are what crosses ranks.
+//
+// Layout of this file: the single-layer kernels (scalar, vector and channel-quad paths); the
+// row reductions, which share one block-reduction tail (block_sum_d) and one finalize
+// (bn_finalize_channel); the multi-layer kernels, whose forward apply and backward reduce are
+// one body each over a memory policy (PtrMem / BufMem) and whose backward apply keeps two
+// forms; the C entry points.  Kernel names are part of the interface (vae2_kernel_log).
 #include <algorithm>
 
 #include "common.h"
@@ -15,14 +21,19 @@
 namespace vae2 {
 
 // ---------------------------------------------------- partial reductions ----
+// Quad-path block shape: quad_rows(C) pixel rows of ceil(C / 4) channel-quad threads, each
+// thread kApplyU pixels per pass.
+static inline int quad_rows(int64_t C) {
+  const int c4 = (int)((C + 3) / 4);
+  return c4 <= 256 ? 256 / c4 : 1;
+}
+constexpr int kApplyU = 4;  // pixels per thread in the apply kernels (2: 852 vs 861, 8: 841 vs 853 frames/s, round-4 A/B)
 // Pixels per block for per-channel reductions: whole passes of the quad-path block
 // (quad_rows(C) pixel rows x kApplyU pixels per thread), as many passes as keep the layer
 // at <= 1024 blocks.  (Round 5 took ceil(P / 1024), at least 32, for every C: the narrow
 // layers' blocks then ran one partial pass -- a 36-channel block covered 64 of the 112
 // pixels its threads load, a 72-channel one 32 of 56 -- and the 18 / 36 / 72 backward
 // reduce launches streamed at 0.34 of the HBM peak.)
-static inline int quad_rows(int64_t C);
-constexpr int kPassU = 4;  // = kApplyU (defined with the apply kernels below)
 int g_bn_blocks = 1024;  // vae2_conv2d_set_tune key 19: blocks per layer (at most, whole passes)
 // vae2_conv2d_set_tune key 20: the multi-layer apply kernels' resident-block budget R (0 =
 // one workgroup per pixel chunk): a launch of T chunks runs ceil(T / ceil(T / R)) workgroups
@@ -31,7 +42,7 @@ int g_bn_blocks = 1024;  // vae2_conv2d_set_tune key 19: blocks per layer (at mo
 int g_bn_apply_res = 0;
 
 static int64_t pix_per_block(int64_t P, int64_t C) {
-  const int64_t pass = (int64_t)quad_rows(C) * kPassU;
+  const int64_t pass = (int64_t)quad_rows(C) * kApplyU;
   const int64_t n = ceil_div(P, (int64_t)g_bn_blocks * pass);
   return pass * (n > 0 ? n : 1);
 }
@@ -136,12 +147,6 @@ __device__ __forceinline__ void st4(float* p, f4 v, int c, int C) {
       if (c + k < C) p[k] = v[k];
   }
 }
-
-static inline int quad_rows(int64_t C) {
-  const int c4 = (int)((C + 3) / 4);
-  return c4 <= 256 ? 256 / c4 : 1;
-}
-constexpr int kApplyU = kPassU;  // pixels per thread in the apply kernels (2: 852 vs 861, 8: 841 vs 853 frames/s, round-4 A/B)
 
 __global__ __launch_bounds__(256) void bn_apply_q_kernel(
     const float* __restrict__ x, Act xd, const float* __restrict__ save,
@@ -347,15 +352,12 @@ __device__ __forceinline__ void rows_sum2(const float* __restrict__ part, int64_
   }
 }
 
-// One block per channel: sums[q][c] (+)= sum_rows part[q][row][c] in double.
-__global__ __launch_bounds__(256) void partials_reduce_kernel(
-    const float* __restrict__ part, int64_t rows, int64_t C, double* sums,
-    int accumulate) {
+// The tail of every block reduction here: the 256 threads' two values summed per wave, the four
+// waves' sums through LDS and added in the fixed order 0 + 1 + 2 + 3.  True on thread 0, whose
+// a and b then hold the block sums; the other threads are done.
+__device__ __forceinline__ bool block_sum_d(double& a, double& b) {
   __shared__ double red[2][4];
-  const int c = blockIdx.x;
   const int tid = threadIdx.x;
-  double a = 0.0, b = 0.0;
-  rows_sum2(part, rows, C, c, tid, a, b);
   a = wave_sum_d(a);
   b = wave_sum_d(b);
   if ((tid & 63) == 0) {
@@ -363,16 +365,77 @@ __global__ __launch_bounds__(256) void partials_reduce_kernel(
     red[1][tid >> 6] = b;
   }
   __syncthreads();
-  if (tid == 0) {
-    double s0 = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    double s1 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    if (accumulate) {
-      sums[c] += s0;
-      sums[C + c] += s1;
-    } else {
-      sums[c] = s0;
-      sums[C + c] = s1;
-    }
+  if (tid != 0) return false;
+  a = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+  b = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+  return true;
+}
+
+// (one value)
+__device__ __forceinline__ bool block_sum_d(double& a) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x;
+  a = wave_sum_d(a);
+  if ((tid & 63) == 0) red[tid >> 6] = a;
+  __syncthreads();
+  if (tid != 0) return false;
+  a = red[0] + red[1] + red[2] + red[3];
+  return true;
+}
+
+// One channel's mean / invstd / scale / shift (save[0 .. 4C)) and running statistics from its
+// (sum, sum of squares) over count elements: the only place these are computed.  L: the
+// layer's parameters (FinArgs, or the multi-layer kernels' FinLayer).  Both spellings of the
+// mean are kept, each caller's bits as they were: SHIFT (the single-layer kernels) adds the
+// optional L.mshift back as m0 + (mshift ? mshift[c] : 0.0), which turns a mean of -0.0 into
+// +0.0; the multi-layer kernels take m0 as it is.
+struct FinArgs {
+  const float* gamma;
+  const float* beta;
+  float* rmean;
+  float* rvar;
+  float* save;
+  float momentum, eps;
+  int64_t C;
+  const float* mshift;
+};
+
+template <bool SHIFT, class Layer, class I>
+__device__ __forceinline__ void bn_finalize_channel(const Layer& L, I c, double s0, double s1,
+                                                    double count) {
+  const double m0 = s0 / count;
+  double var = s1 / count - m0 * m0;
+  if (var < 0.0) var = 0.0;
+  double mean = m0;
+  if constexpr (SHIFT) mean = m0 + (L.mshift ? (double)L.mshift[c] : 0.0);
+  const double invstd = 1.0 / sqrt(var + (double)L.eps);
+  const float gm = L.gamma ? L.gamma[c] : 1.f;
+  const float bt = L.beta ? L.beta[c] : 0.f;
+  L.save[c] = (float)mean;
+  L.save[L.C + c] = (float)invstd;
+  L.save[2 * L.C + c] = (float)(gm * invstd);
+  L.save[3 * L.C + c] = (float)(bt - mean * (gm * invstd));
+  if (L.rmean) {
+    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
+    L.rmean[c] = (float)((1.0 - L.momentum) * L.rmean[c] + L.momentum * mean);
+    L.rvar[c] = (float)((1.0 - L.momentum) * L.rvar[c] + L.momentum * unbiased);
+  }
+}
+
+// One block per channel: sums[q][c] (+)= sum_rows part[q][row][c] in double.
+__global__ __launch_bounds__(256) void partials_reduce_kernel(
+    const float* __restrict__ part, int64_t rows, int64_t C, double* sums,
+    int accumulate) {
+  const int c = blockIdx.x;
+  double s0 = 0.0, s1 = 0.0;
+  rows_sum2(part, rows, C, c, threadIdx.x, s0, s1);
+  if (!block_sum_d(s0, s1)) return;
+  if (accumulate) {
+    sums[c] += s0;
+    sums[C + c] += s1;
+  } else {
+    sums[c] = s0;
+    sums[C + c] = s1;
   }
 }
 
@@ -388,21 +451,10 @@ __global__ __launch_bounds__(256) void reduce_then_kernel(
     const float* gamma, const float* beta, float* rmean, float* rvar, int64_t* nbt,
     float momentum, float eps, float* save, float* dgamma, float* dbeta,
     const float* mshift = nullptr) {
-  __shared__ double red[2][4];
   const int c = blockIdx.x;
-  const int tid = threadIdx.x;
-  double a = 0.0, b = 0.0;
-  rows_sum2(part, rows, C, c, tid, a, b);
-  a = wave_sum_d(a);
-  b = wave_sum_d(b);
-  if ((tid & 63) == 0) {
-    red[0][tid >> 6] = a;
-    red[1][tid >> 6] = b;
-  }
-  __syncthreads();
-  if (tid != 0) return;
-  const double s0 = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-  const double s1 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+  double s0 = 0.0, s1 = 0.0;
+  rows_sum2(part, rows, C, c, threadIdx.x, s0, s1);
+  if (!block_sum_d(s0, s1)) return;
   sums[c] = s0;
   sums[C + c] = s1;
   if (MODE == 1) {
@@ -411,22 +463,8 @@ __global__ __launch_bounds__(256) void reduce_then_kernel(
     return;
   }
   if (c == 0 && nbt) nbt[0] += 1;
-  const double m0 = s0 / count;
-  double var = s1 / count - m0 * m0;
-  if (var < 0.0) var = 0.0;
-  const double mean = m0 + (mshift ? (double)mshift[c] : 0.0);
-  const double invstd = 1.0 / sqrt(var + (double)eps);
-  const float gm = gamma ? gamma[c] : 1.f;
-  const float bt = beta ? beta[c] : 0.f;
-  save[c] = (float)mean;
-  save[C + c] = (float)invstd;
-  save[2 * C + c] = (float)(gm * invstd);
-  save[3 * C + c] = (float)(bt - mean * (gm * invstd));
-  if (rmean) {
-    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    rmean[c] = (float)((1.0 - momentum) * rmean[c] + momentum * mean);
-    rvar[c] = (float)((1.0 - momentum) * rvar[c] + momentum * unbiased);
-  }
+  bn_finalize_channel<true>(FinArgs{gamma, beta, rmean, rvar, save, momentum, eps, C, mshift}, c,
+                            s0, s1, count);
 }
 
 __global__ void bn_finalize_kernel(const double* sums, double count,
@@ -437,24 +475,8 @@ __global__ void bn_finalize_kernel(const double* sums, double count,
   int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (c == 0 && nbt) nbt[0] += 1;
   if (c >= C) return;
-  const double m0 = sums[c] / count;
-  double var = sums[C + c] / count - m0 * m0;
-  if (var < 0.0) var = 0.0;
-  const double mean = m0 + (mshift ? (double)mshift[c] : 0.0);
-  double invstd = 1.0 / sqrt(var + (double)eps);
-  float g = gamma ? gamma[c] : 1.f;
-  float b = beta ? beta[c] : 0.f;
-  float scale = (float)(g * invstd);
-  float shift = (float)(b - mean * (g * invstd));
-  save[c] = (float)mean;
-  save[C + c] = (float)invstd;
-  save[2 * C + c] = scale;
-  save[3 * C + c] = shift;
-  if (rmean) {
-    double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    rmean[c] = (float)((1.0 - momentum) * rmean[c] + momentum * mean);
-    rvar[c] = (float)((1.0 - momentum) * rvar[c] + momentum * unbiased);
-  }
+  bn_finalize_channel<true>(FinArgs{gamma, beta, rmean, rvar, save, momentum, eps, C, mshift}, c,
+                            sums[c], sums[C + c], count);
 }
 
 __global__ void bn_eval_kernel(const float* gamma, const float* beta,
@@ -558,20 +580,12 @@ __global__ void bn_param_grad_kernel(const double* sums, int64_t C,
 __global__ __launch_bounds__(256) void colsum_to_float_kernel(
     const float* __restrict__ part, int64_t rows, int64_t C, float* out,
     int accumulate) {
-  __shared__ double red[4];
-  const int c = blockIdx.x, tid = threadIdx.x;
-  double a = 0.0;
-  {
-    double b = 0.0;
-    rows_sum2(part, rows, C, c, tid, a, b, false);
-  }
-  a = wave_sum_d(a);
-  if ((tid & 63) == 0) red[tid >> 6] = a;
-  __syncthreads();
-  if (tid == 0) {
-    float s = (float)(red[0] + red[1] + red[2] + red[3]);
-    out[c] = accumulate ? out[c] + s : s;
-  }
+  const int c = blockIdx.x;
+  double a = 0.0, b = 0.0;
+  rows_sum2(part, rows, C, c, threadIdx.x, a, b, false);
+  if (!block_sum_d(a)) return;
+  const float s = (float)a;
+  out[c] = accumulate ? out[c] + s : s;
 }
 
 // ------------------------------------------------ multi-layer launches ----
@@ -619,7 +633,8 @@ struct BnMulti {
   int total;  // pixel chunks of the launch (apply kernels: workgroups stride over them)
 };
 
-// vae2_conv2d_set_tune key 8: 0 = the round-4 pointer-arithmetic BatchNorm bodies (A/B)
+// vae2_conv2d_set_tune key 8: 0 = the multi-layer kernels address memory by 64-bit pointer
+// arithmetic (PtrMem, the *_r4_kernel names) instead of buffer resources (BufMem); A/B
 int g_bn_v2 = 1;
 
 __device__ __forceinline__ int bn_layer_of(const BnMulti& m, int b) {
@@ -628,40 +643,145 @@ __device__ __forceinline__ int bn_layer_of(const BnMulti& m, int b) {
   return i;
 }
 
+// ---------------------------------------------------- memory policies ----
+// bn_apply_body and bn_bwd_reduce_body below are written once and take one of two policies
+// for how they address memory.  A policy provides exactly what differs between the two
+// forms: pixel access (the 16-byte load of channel quad c of pixel p, the mask byte), the
+// quad store (to a position or to none() for a pixel outside, given the quad's valid channel
+// count) and the fetch of a per-channel coefficient quad (row j of a [rows][C] array).
+//
+// The two policies give the same bits in every valid channel.  Lanes past C of a partial quad
+// see different coefficients (PtrMem: 0; BufMem: the next row's, or the clamped channel's) and
+// are never stored, except into the forward mask byte's bits of channels >= C: those bits
+// differ between the policies, and no kernel reads them.
+//
+// PtrMem: 64-bit pointer arithmetic from the base pointers, any extent.  Stores are branched
+// around (pixel outside: skipped; partial quad: per channel), coefficients are per-channel
+// loads of clamped channels, 0 past C (chan4).
+struct PtrMem {
+  typedef int64_t Idx;                         // pixel index
+  struct Tensor { float* b; const int& ps; };  // ps: the layer's pixel stride field
+  typedef uint8_t* Bytes;
+  typedef const float* Rows;
+  typedef float* Pos;  // where a quad lies
+  static __device__ __forceinline__ Tensor tensor(const float* b, Idx, const int& ps, bool = true) {
+    return Tensor{const_cast<float*>(b), ps};
+  }
+  static __device__ __forceinline__ Bytes bytes(const uint8_t* b, Idx, int, bool = true) {
+    return const_cast<uint8_t*>(b);
+  }
+  static __device__ __forceinline__ Pos at(const Tensor& t, Idx p, int c) { return t.b + p * t.ps + c; }
+  static __device__ __forceinline__ Pos none() { return nullptr; }
+  static __device__ __forceinline__ f4 load(const Tensor& t, Idx p, int c) { return ld4(at(t, p, c)); }
+  static __device__ __forceinline__ uint32_t load_byte(Bytes m, Idx i) { return m[i]; }
+  static __device__ __forceinline__ void store(const Tensor&, Pos o, int nv, bool, f4 v) {
+    if (o) st4(o, v, 0, nv);
+  }
+  static __device__ __forceinline__ void store_byte(Bytes m, uint8_t v, Idx i, bool in) {
+    if (in) m[i] = v;
+  }
+  static __device__ __forceinline__ Rows rows(const float* b, uint32_t) { return b; }
+  static __device__ __forceinline__ f4 row4(Rows b, int j, bool, int c, int C) { return chan4(b + j * C, c, C); }
+};
+
+// BufMem: one buffer resource per tensor and 32-bit byte offsets -- every extent < 2 GB (host
+// check, bn_multi_launch).  No per-lane branches: pixels past P are clamped for the loads and
+// dropped for the stores (out-of-range offset), partial channel quads are stored by
+// store_quad (chosen on the uniform `part`).
+// Per-channel coefficients: a 16-byte load of the quad where it stays inside the buffer (a
+// partial quad then reads the next coefficient row: only its dropped lanes use those),
+// per-channel loads of clamped channels for the last row of a buffer (a 16-byte load that
+// crosses the end of the range returns 0 in every lane).
+struct BufMem {
+  typedef uint32_t Idx;
+  struct Tensor { __amdgpu_buffer_rsrc_t r; const int& ps; };
+  typedef __amdgpu_buffer_rsrc_t Bytes;
+  typedef __amdgpu_buffer_rsrc_t Rows;
+  typedef uint32_t Pos;  // byte offset
+  static __device__ __forceinline__ Tensor tensor(const float* b, Idx P, const int& ps) {
+    return Tensor{make_rsrc(b, P * (uint32_t)ps * 4u), ps};
+  }
+  static __device__ __forceinline__ Tensor tensor(const float* b, Idx P, const int& ps, bool on) {
+    return Tensor{make_rsrc(b, on ? P * (uint32_t)ps * 4u : 0u), ps};  // (an optional operand)
+  }
+  static __device__ __forceinline__ Bytes bytes(const uint8_t* b, Idx P, int c4) {
+    return make_rsrc(b, P * (uint32_t)c4);
+  }
+  static __device__ __forceinline__ Bytes bytes(const uint8_t* b, Idx P, int c4, bool on) {
+    return make_rsrc(b, on ? P * (uint32_t)c4 : 0u);
+  }
+  static __device__ __forceinline__ Pos at(const Tensor& t, Idx p, int c) {
+    return (p * (uint32_t)t.ps + (uint32_t)c) * 4u;
+  }
+  static __device__ __forceinline__ Pos none() { return kOOB; }
+  static __device__ __forceinline__ f4 load(const Tensor& t, Idx p, int c) { return load4(t.r, at(t, p, c)); }
+  static __device__ __forceinline__ uint32_t load_byte(Bytes m, Idx i) { return load_u8(m, i); }
+  static __device__ __forceinline__ void store(const Tensor& t, Pos o, int nv, bool part, f4 v) {
+    if (part) store_quad(t.r, o, v, nv);
+    else store4(t.r, o, v);
+  }
+  static __device__ __forceinline__ void store_byte(Bytes m, uint8_t v, Idx i, bool in) {
+    __builtin_amdgcn_raw_buffer_store_b8(v, m, in ? i : kOOB, 0, 0);
+  }
+  static __device__ __forceinline__ Rows rows(const float* b, uint32_t bytes) { return make_rsrc(b, bytes); }
+  static __device__ __forceinline__ f4 row4(Rows r, int j, bool last, int c, int C) {
+    const uint32_t row = (uint32_t)j * ((uint32_t)C * 4u);
+    if (!last) return load4(r, row + 4u * (uint32_t)c);
+    f4 v;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = load1(r, row + 4u * (uint32_t)(c + k < C ? c + k : C - 1));
+    return v;
+  }
+};
+
+// Forward apply of one layer's pixel chunk blk.
+template <class Mem>
 __device__ __forceinline__ void bn_apply_body(const BnLayer& L, int blk) {
+  typedef typename Mem::Idx Idx;
   const int C = L.C, c4 = (C + 3) >> 2;
   const int tid = threadIdx.x;
   if (tid >= L.rows * c4) return;
   const int r = tid / c4, c = 4 * (tid - r * c4);
-  const f4 sc = chan4(L.save + 2 * C, c, C), sh = chan4(L.save + 3 * C, c, C);
-  f4 rsc = {0.f, 0.f, 0.f, 0.f}, rsh = rsc;
-  if (L.rx) { rsc = chan4(L.rsave + 2 * C, c, C); rsh = chan4(L.rsave + 3 * C, c, C); }
-  const int64_t pb = (int64_t)blk * L.rows * kApplyU + r;
+  const int nv = C - c < 4 ? C - c : 4;  // valid channels of this quad
+  const bool part = (C & 3) != 0;        // (uniform) some quad is partial
+  const Idx P = (Idx)L.P;
+  const uint32_t cb = (uint32_t)C * 4u;  // bytes of a coefficient row
+  const typename Mem::Rows rs = Mem::rows(L.save, 4u * cb);
+  const typename Mem::Tensor tx = Mem::tensor(L.x, P, L.x_ps);
+  const typename Mem::Tensor to = Mem::tensor(L.o, P, L.o_ps);
+  const Idx pb = (Idx)blk * (Idx)(L.rows * kApplyU) + (Idx)r;
   // every load unconditional (pixels past P re-read pixel P-1, never stored) and the
   // uniform branches outside the pixel loop, so the loads of all pixels go out together
+  Idx pp[kApplyU];
+  bool in[kApplyU];
+#pragma unroll
+  for (int u = 0; u < kApplyU; ++u) {
+    const Idx p = pb + (Idx)(u * L.rows);
+    in[u] = p < P;
+    pp[u] = in[u] ? p : P - 1;
+  }
   f4 v[kApplyU], rv[kApplyU];
 #pragma unroll
-  for (int u = 0; u < kApplyU; ++u) {
-    const int64_t p = pb + u * L.rows < L.P ? pb + u * L.rows : L.P - 1;
-    v[u] = ld4(L.x + p * L.x_ps + c);
-  }
+  for (int u = 0; u < kApplyU; ++u) v[u] = Mem::load(tx, pp[u], c);
   if (L.a) {
+    const typename Mem::Tensor ta = Mem::tensor(L.a, P, L.a_ps);
 #pragma unroll
-    for (int u = 0; u < kApplyU; ++u) {
-      const int64_t p = pb + u * L.rows < L.P ? pb + u * L.rows : L.P - 1;
-      rv[u] = ld4(L.a + p * L.a_ps + c);
-    }
+    for (int u = 0; u < kApplyU; ++u) rv[u] = Mem::load(ta, pp[u], c);
   } else if (L.rx) {
+    const typename Mem::Tensor tr = Mem::tensor(L.rx, P, L.rx_ps);
 #pragma unroll
-    for (int u = 0; u < kApplyU; ++u) {
-      const int64_t p = pb + u * L.rows < L.P ? pb + u * L.rows : L.P - 1;
-      rv[u] = ld4(L.rx + p * L.rx_ps + c);
-    }
+    for (int u = 0; u < kApplyU; ++u) rv[u] = Mem::load(tr, pp[u], c);
   }
+  const f4 sc = Mem::row4(rs, 2, false, c, C), sh = Mem::row4(rs, 3, true, c, C);
+  f4 rsc = {0.f, 0.f, 0.f, 0.f}, rsh = rsc;
+  if (L.rx) {
+    const typename Mem::Rows rrs = Mem::rows(L.rsave, 4u * cb);
+    rsc = Mem::row4(rrs, 2, false, c, C);
+    rsh = Mem::row4(rrs, 3, true, c, C);
+  }
+  const typename Mem::Bytes tm = Mem::bytes(L.mk, P, c4, L.mk != nullptr);
 #pragma unroll
   for (int u = 0; u < kApplyU; ++u) {
-    const int64_t p = pb + u * L.rows;
-    if (p >= L.P) break;
     f4 o;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -671,190 +791,34 @@ __device__ __forceinline__ void bn_apply_body(const BnLayer& L, int blk) {
       else if (L.rx) t += __builtin_fmaf(rv[u][k], rsc[k], rsh[k]);
       o[k] = (L.relu && t < 0.f) ? 0.f : t;  // NaN propagates (torch.relu)
     }
-    st4(L.o + p * L.o_ps + c, o, c, C);
+    Mem::store(to, in[u] ? Mem::at(to, pp[u], c) : Mem::none(), nv, part, o);
     if (L.mk)  // threshold_backward's test (y > 0: NaN and 0 cut the gradient)
-      L.mk[p * c4 + (c >> 2)] = (uint8_t)((o[0] > 0.f) | ((o[1] > 0.f) << 1) |
-                                          ((o[2] > 0.f) << 2) | ((o[3] > 0.f) << 3));
-  }
-}
-
-// Buffer-resource form of bn_apply_body (same arithmetic; see bn_bwd_apply_body2).
-__device__ __forceinline__ void bn_apply_body2(const BnLayer& L, int blk) {
-  const int C = L.C, c4 = (C + 3) >> 2;
-  const int tid = threadIdx.x;
-  if (tid >= L.rows * c4) return;
-  const int r = tid / c4, c = 4 * (tid - r * c4);
-  const int nv = C - c < 4 ? C - c : 4;
-  const bool part = (C & 3) != 0;
-  const uint32_t P = (uint32_t)L.P;
-  const uint32_t cb = (uint32_t)C * 4u;
-  const __amdgpu_buffer_rsrc_t rs = make_rsrc(L.save, 4u * cb);
-  const __amdgpu_buffer_rsrc_t rx = make_rsrc(L.x, P * (uint32_t)L.x_ps * 4u);
-  const __amdgpu_buffer_rsrc_t ro = make_rsrc(L.o, P * (uint32_t)L.o_ps * 4u);
-  const uint32_t pb = (uint32_t)blk * (uint32_t)(L.rows * kApplyU) + (uint32_t)r;
-  uint32_t pp[kApplyU];
-  bool in[kApplyU];
-#pragma unroll
-  for (int u = 0; u < kApplyU; ++u) {
-    const uint32_t p = pb + (uint32_t)(u * L.rows);
-    in[u] = p < P;
-    pp[u] = in[u] ? p : P - 1;
-  }
-  f4 v[kApplyU], rv[kApplyU];
-#pragma unroll
-  for (int u = 0; u < kApplyU; ++u) v[u] = load4(rx, (pp[u] * (uint32_t)L.x_ps + (uint32_t)c) * 4u);
-  if (L.a) {
-    const __amdgpu_buffer_rsrc_t ra = make_rsrc(L.a, P * (uint32_t)L.a_ps * 4u);
-#pragma unroll
-    for (int u = 0; u < kApplyU; ++u) rv[u] = load4(ra, (pp[u] * (uint32_t)L.a_ps + (uint32_t)c) * 4u);
-  } else if (L.rx) {
-    const __amdgpu_buffer_rsrc_t rr = make_rsrc(L.rx, P * (uint32_t)L.rx_ps * 4u);
-#pragma unroll
-    for (int u = 0; u < kApplyU; ++u) rv[u] = load4(rr, (pp[u] * (uint32_t)L.rx_ps + (uint32_t)c) * 4u);
-  }
-  auto last_row4 = [&](__amdgpu_buffer_rsrc_t rr, uint32_t row) {
-    f4 t;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) t[k] = load1(rr, row + 4u * (uint32_t)(c + k < C ? c + k : C - 1));
-    return t;
-  };
-  const f4 sc = load4(rs, 2u * cb + 4u * (uint32_t)c), sh = last_row4(rs, 3u * cb);
-  f4 rsc = {0.f, 0.f, 0.f, 0.f}, rsh = rsc;
-  if (L.rx) {
-    const __amdgpu_buffer_rsrc_t rrs = make_rsrc(L.rsave, 4u * cb);
-    rsc = load4(rrs, 2u * cb + 4u * (uint32_t)c);
-    rsh = last_row4(rrs, 3u * cb);
-  }
-  const __amdgpu_buffer_rsrc_t rm = make_rsrc(L.mk, L.mk ? P * (uint32_t)c4 : 0u);
-#pragma unroll
-  for (int u = 0; u < kApplyU; ++u) {
-    f4 o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float t = __builtin_fmaf(v[u][k], sc[k], sh[k]);
-      if (L.a) t += rv[u][k];
-      else if (L.rx) t += __builtin_fmaf(rv[u][k], rsc[k], rsh[k]);
-      o[k] = (L.relu && t < 0.f) ? 0.f : t;  // NaN propagates (torch.relu)
-    }
-    const uint32_t off = in[u] ? (pp[u] * (uint32_t)L.o_ps + (uint32_t)c) * 4u : kOOB;
-    if (part) store_quad(ro, off, o, nv);
-    else store4(ro, off, o);
-    if (L.mk)  // threshold_backward's test (y > 0: NaN and 0 cut the gradient)
-      __builtin_amdgcn_raw_buffer_store_b8(
-          (uint8_t)((o[0] > 0.f) | ((o[1] > 0.f) << 1) | ((o[2] > 0.f) << 2) | ((o[3] > 0.f) << 3)),
-          rm, in[u] ? pp[u] * (uint32_t)c4 + (uint32_t)(c >> 2) : kOOB, 0, 0);
+      Mem::store_byte(tm, (uint8_t)((o[0] > 0.f) | ((o[1] > 0.f) << 1) | ((o[2] > 0.f) << 2) |
+                                    ((o[3] > 0.f) << 3)),
+                      pp[u] * (Idx)c4 + (Idx)(c >> 2), in[u]);
   }
 }
 
 __global__ __launch_bounds__(256) void bn_apply_multi_kernel(BnMulti m) {
   for (int b = blockIdx.x; b < m.total; b += gridDim.x) {  // (once unless key 20 is set)
     const int i = bn_layer_of(m, b);
-    bn_apply_body2(m.L[i], b - m.L[i].blk0);
+    bn_apply_body<BufMem>(m.L[i], b - m.L[i].blk0);
   }
 }
 
 __global__ __launch_bounds__(256) void bn_apply_multi_r4_kernel(BnMulti m) {
   const int i = bn_layer_of(m, blockIdx.x);
-  bn_apply_body(m.L[i], blockIdx.x - m.L[i].blk0);
+  bn_apply_body<PtrMem>(m.L[i], blockIdx.x - m.L[i].blk0);
 }
 
 // Backward partials (sum g, sum g*xhat) of one layer's pixel range blk*ppb ...
+// ACT (compile time, so the unused operand arrays cost no registers): how the ReLU mask is
+// known -- 0 recomputed from x (or no ReLU), 1 mask bytes, 2 stored y, 3 decided per layer;
+// RB: some layer has a residual BatchNorm (rx).
+template <class Mem, int ACT, bool RB>
 __device__ __forceinline__ void bn_bwd_reduce_body(const BnLayer& L, int blk, int nblk,
                                                    float* red0, float* red1) {
-  const int C = L.C, c4 = (C + 3) >> 2;
-  const int tid = threadIdx.x;
-  const int64_t p0 = blk * L.ppb;
-  int64_t p1 = p0 + L.ppb;
-  if (p1 > L.P) p1 = L.P;
-  f4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s0;
-  const int r = tid / c4, c = 4 * (tid - r * c4);
-  const uint8_t* mk = L.relu ? L.mk : nullptr;  // stored mask, else y, else from x
-  const float* y = L.relu && !mk ? L.a : nullptr;
-  const bool rb = L.rx != nullptr;  // + the residual BN's sum g * xhat_r (same g)
-  if (tid < L.rows * c4) {
-    const f4 mean = chan4(L.save, c, C), invstd = chan4(L.save + C, c, C);
-    const f4 sc = chan4(L.save + 2 * C, c, C), sh = chan4(L.save + 3 * C, c, C);
-    f4 rmean = s0, rinv = s0;
-    if (rb) { rmean = chan4(L.rsave, c, C); rinv = chan4(L.rsave + C, c, C); }
-    // kApplyU pixels' loads in flight per thread, then their math in pixel order (the
-    // same accumulation order as one pixel at a time)
-    for (int64_t pb = p0 + r; pb < p1; pb += (int64_t)kApplyU * L.rows) {
-      f4 xv[kApplyU], gv[kApplyU], yv[kApplyU], rv[kApplyU];
-      uint32_t mv[kApplyU];
-      // unconditional loads (pixels past p1 re-read p1 - 1, not summed), uniform branches
-      // outside the pixel loop: all pixels' loads in flight together
-      int64_t pp[kApplyU];
-#pragma unroll
-      for (int u = 0; u < kApplyU; ++u) pp[u] = pb + u * L.rows < p1 ? pb + u * L.rows : p1 - 1;
-#pragma unroll
-      for (int u = 0; u < kApplyU; ++u) {
-        xv[u] = ld4(L.x + pp[u] * L.x_ps + c);
-        gv[u] = ld4(L.dy + pp[u] * L.dy_ps + c);
-      }
-      if (y) {
-#pragma unroll
-        for (int u = 0; u < kApplyU; ++u) yv[u] = ld4(y + pp[u] * L.a_ps + c);
-      }
-      if (mk) {
-#pragma unroll
-        for (int u = 0; u < kApplyU; ++u) mv[u] = mk[pp[u] * c4 + (c >> 2)];
-      }
-      if (rb) {
-#pragma unroll
-        for (int u = 0; u < kApplyU; ++u) rv[u] = ld4(L.rx + pp[u] * L.rx_ps + c);
-      }
-#pragma unroll
-      for (int u = 0; u < kApplyU; ++u) {
-        if (pb + u * L.rows >= p1) break;
-        const f4 xa = xv[u];
-        f4 ga = gv[u];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if (L.relu && !(mk ? ((mv[u] >> k) & 1u) != 0
-                             : (y ? yv[u][k] : __builtin_fmaf(xa[k], sc[k], sh[k])) > 0.f))
-            ga[k] = 0.f;
-          s0[k] += ga[k];
-          s1[k] += ga[k] * (xa[k] - mean[k]) * invstd[k];
-          if (rb) s2[k] += ga[k] * (rv[u][k] - rmean[k]) * rinv[k];
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      red0[r * 4 * c4 + c + k] = s0[k];
-      red1[r * 4 * c4 + c + k] = s1[k];
-    }
-  }
-  __syncthreads();
-  for (int ch = tid; ch < C; ch += 256) {
-    float a = 0.f, b = 0.f;
-    for (int i = 0; i < L.rows; ++i) {
-      a += red0[i * 4 * c4 + ch];
-      b += red1[i * 4 * c4 + ch];
-    }
-    L.part[(int64_t)blk * C + ch] = a;
-    L.part[((int64_t)nblk + blk) * C + ch] = b;
-    if (rb) L.rpart[(int64_t)blk * C + ch] = a;  // the residual BN's sum g: the same sum
-  }
-  if (!rb) return;
-  __syncthreads();
-  if (tid < L.rows * c4) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) red1[r * 4 * c4 + c + k] = s2[k];
-  }
-  __syncthreads();
-  for (int ch = tid; ch < C; ch += 256) {
-    float b = 0.f;
-    for (int i = 0; i < L.rows; ++i) b += red1[i * 4 * c4 + ch];
-    L.rpart[((int64_t)nblk + blk) * C + ch] = b;
-  }
-}
-
-// Buffer-resource form of bn_bwd_reduce_body (same arithmetic and summation order),
-// specialised like bn_bwd_apply_body2 (ACT: ReLU mask source, RB: residual BatchNorm).
-template <int ACT, bool RB>
-__device__ __forceinline__ void bn_bwd_reduce_body2(const BnLayer& L, int blk, int nblk,
-                                                   float* red0, float* red1) {
+  typedef typename Mem::Idx Idx;
   const int C = L.C, c4 = (C + 3) >> 2;
   const int tid = threadIdx.x;
   const int64_t p0 = blk * L.ppb;
@@ -866,12 +830,12 @@ __device__ __forceinline__ void bn_bwd_reduce_body2(const BnLayer& L, int blk, i
   const uint8_t* mk = L.relu && (ACT == 1 || ACT == 3) ? L.mk : nullptr;
   const float* y = L.relu && (ACT == 2 || (ACT == 3 && !mk)) ? L.a : nullptr;
   const bool rb = RB && L.rx != nullptr;  // + the residual BN's sum g * xhat_r (same g)
-  const uint32_t P = (uint32_t)L.P;
-  const __amdgpu_buffer_rsrc_t rxx = make_rsrc(L.x, P * (uint32_t)L.x_ps * 4u);
-  const __amdgpu_buffer_rsrc_t rdy = make_rsrc(L.dy, P * (uint32_t)L.dy_ps * 4u);
-  const __amdgpu_buffer_rsrc_t ry = make_rsrc(y, y ? P * (uint32_t)L.a_ps * 4u : 0u);
-  const __amdgpu_buffer_rsrc_t rm = make_rsrc(mk, mk ? P * (uint32_t)c4 : 0u);
-  const __amdgpu_buffer_rsrc_t rr = make_rsrc(L.rx, rb ? P * (uint32_t)L.rx_ps * 4u : 0u);
+  const Idx P = (Idx)L.P;
+  const typename Mem::Tensor tx = Mem::tensor(L.x, P, L.x_ps);
+  const typename Mem::Tensor tdy = Mem::tensor(L.dy, P, L.dy_ps);
+  const typename Mem::Tensor ty = Mem::tensor(y, P, L.a_ps, y != nullptr);
+  const typename Mem::Bytes tm = Mem::bytes(mk, P, c4, mk != nullptr);
+  const typename Mem::Tensor tr = Mem::tensor(L.rx, P, L.rx_ps, rb);
   if (tid < L.rows * c4) {
     const f4 mean = chan4(L.save, c, C), invstd = chan4(L.save + C, c, C);
     const f4 sc = chan4(L.save + 2 * C, c, C), sh = chan4(L.save + 3 * C, c, C);
@@ -884,26 +848,26 @@ __device__ __forceinline__ void bn_bwd_reduce_body2(const BnLayer& L, int blk, i
       uint32_t mv[kApplyU];
       // unconditional loads (pixels past p1 re-read p1 - 1, not summed), uniform branches
       // outside the pixel loop: all pixels' loads in flight together
-      uint32_t pp[kApplyU];
+      Idx pp[kApplyU];
 #pragma unroll
       for (int u = 0; u < kApplyU; ++u)
-        pp[u] = (uint32_t)(pb + u * L.rows < p1 ? pb + u * L.rows : p1 - 1);
+        pp[u] = (Idx)(pb + u * L.rows < p1 ? pb + u * L.rows : p1 - 1);
 #pragma unroll
       for (int u = 0; u < kApplyU; ++u) {
-        xv[u] = load4(rxx, (pp[u] * (uint32_t)L.x_ps + (uint32_t)c) * 4u);
-        gv[u] = load4(rdy, (pp[u] * (uint32_t)L.dy_ps + (uint32_t)c) * 4u);
+        xv[u] = Mem::load(tx, pp[u], c);
+        gv[u] = Mem::load(tdy, pp[u], c);
       }
       if (y) {
 #pragma unroll
-        for (int u = 0; u < kApplyU; ++u) yv[u] = load4(ry, (pp[u] * (uint32_t)L.a_ps + (uint32_t)c) * 4u);
+        for (int u = 0; u < kApplyU; ++u) yv[u] = Mem::load(ty, pp[u], c);
       }
       if (mk) {
 #pragma unroll
-        for (int u = 0; u < kApplyU; ++u) mv[u] = load_u8(rm, pp[u] * (uint32_t)c4 + (uint32_t)(c >> 2));
+        for (int u = 0; u < kApplyU; ++u) mv[u] = Mem::load_byte(tm, pp[u] * (Idx)c4 + (Idx)(c >> 2));
       }
       if (rb) {
 #pragma unroll
-        for (int u = 0; u < kApplyU; ++u) rv[u] = load4(rr, (pp[u] * (uint32_t)L.rx_ps + (uint32_t)c) * 4u);
+        for (int u = 0; u < kApplyU; ++u) rv[u] = Mem::load(tr, pp[u], c);
       }
 #pragma unroll
       for (int u = 0; u < kApplyU; ++u) {
@@ -953,44 +917,28 @@ __device__ __forceinline__ void bn_bwd_reduce_body2(const BnLayer& L, int blk, i
 }
 
 // nblk of layer i = blk0[i+1] - blk0[i] (the last: gridDim.x - blk0)
-template <int ACT, bool RB>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_multi_kernel(BnMulti m) {
+template <class Mem, int ACT, bool RB>
+__device__ __forceinline__ void bn_bwd_reduce_block(const BnMulti& m) {
   __shared__ float red[2][256 * 4];
   const int i = bn_layer_of(m, blockIdx.x);
   const int nblk = (i + 1 < m.n ? m.L[i + 1].blk0 : (int)gridDim.x) - m.L[i].blk0;
-  bn_bwd_reduce_body2<ACT, RB>(m.L[i], blockIdx.x - m.L[i].blk0, nblk, red[0], red[1]);
+  bn_bwd_reduce_body<Mem, ACT, RB>(m.L[i], blockIdx.x - m.L[i].blk0, nblk, red[0], red[1]);
 }
 
-static void bwd_reduce_launch(const BnMulti& m, unsigned blocks, hipStream_t st) {
-  int act = -1;
-  bool rb = false;
-  for (int j = 0; j < m.n; ++j) {
-    const BnLayer& L = m.L[j];
-    const int a = !L.relu ? 0 : (L.mk ? 1 : (L.a ? 2 : 0));
-    act = act < 0 ? a : (act == a ? act : 3);
-    rb = rb || L.rx;
-  }
-#define BWR(A)                                                                                    \
-  do {                                                                                            \
-    if (rb) VAE2_LAUNCH((bn_bwd_reduce_multi_kernel<A, true>), dim3(blocks), dim3(256), 0, st, m); \
-    else VAE2_LAUNCH((bn_bwd_reduce_multi_kernel<A, false>), dim3(blocks), dim3(256), 0, st, m);   \
-  } while (0)
-  switch (act) {
-    case 0: BWR(0); break;
-    case 1: BWR(1); break;
-    case 2: BWR(2); break;
-    default: BWR(3); break;
-  }
-#undef BWR
+template <int ACT, bool RB>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_multi_kernel(BnMulti m) {
+  bn_bwd_reduce_block<BufMem, ACT, RB>(m);
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_reduce_multi_r4_kernel(BnMulti m) {
-  __shared__ float red[2][256 * 4];
-  const int i = bn_layer_of(m, blockIdx.x);
-  const int nblk = (i + 1 < m.n ? m.L[i + 1].blk0 : (int)gridDim.x) - m.L[i].blk0;
-  bn_bwd_reduce_body(m.L[i], blockIdx.x - m.L[i].blk0, nblk, red[0], red[1]);
+  bn_bwd_reduce_block<PtrMem, 3, true>(m);
 }
 
+// The backward apply keeps two hand-written forms: this pointer form (key 8 = 0, extents of
+// 2 GB or more) and bn_bwd_apply_body2 below.  They agree bit for bit (test_bn_gpu.py:
+// test_multi_r4_matches_default_bits), but their coefficient fetch and store addressing
+// diverge too far for the two policies above: a merged body needed the fp64 sums rows in two phases and the dropped-store offsets of
+// body2 spelled out in it, and was neither shorter nor clearer.
 __device__ __forceinline__ void bn_bwd_apply_body(const BnLayer& L, int blk) {
   const int C = L.C, c4 = (C + 3) >> 2;
   const int tid = threadIdx.x;
@@ -1238,37 +1186,45 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_multi_kernel(BnMulti m) {
   }
 }
 
-// The specialisation of a launch: the union of its layers' features.
-static void bwd_apply_launch(const BnMulti& m, unsigned blocks, hipStream_t st) {
-  int act = -1;
-  bool rb = false, dacc = false;
-  for (int j = 0; j < m.n; ++j) {
-    const BnLayer& L = m.L[j];
-    const int a = !L.relu ? 0 : (L.mk ? 1 : (L.a ? 2 : 0));
-    act = act < 0 ? a : (act == a ? act : 3);
-    rb = rb || L.rx;
-    dacc = dacc || (L.dres && L.dres_acc);
-  }
-#define BWA(A)                                                                                  \
-  do {                                                                                          \
-    if (rb && dacc) VAE2_LAUNCH((bn_bwd_apply_multi_kernel<A, true, true>), dim3(blocks), dim3(256), 0, st, m); \
-    else if (rb) VAE2_LAUNCH((bn_bwd_apply_multi_kernel<A, true, false>), dim3(blocks), dim3(256), 0, st, m);   \
-    else if (dacc) VAE2_LAUNCH((bn_bwd_apply_multi_kernel<A, false, true>), dim3(blocks), dim3(256), 0, st, m); \
-    else VAE2_LAUNCH((bn_bwd_apply_multi_kernel<A, false, false>), dim3(blocks), dim3(256), 0, st, m);          \
-  } while (0)
-  switch (act) {
-    case 0: BWA(0); break;
-    case 1: BWA(1); break;
-    case 2: BWA(2); break;
-    default: BWA(3); break;
-  }
-#undef BWA
-}
-
 __global__ __launch_bounds__(256) void bn_bwd_apply_multi_r4_kernel(BnMulti m) {
   const int i = bn_layer_of(m, blockIdx.x);
   bn_bwd_apply_body(m.L[i], blockIdx.x - m.L[i].blk0);
 }
+
+// The specialisation of a launch: the union of its layers' features.
+struct BnFeatures {
+  int act;  // 0 .. 2: every layer's ReLU mask source (ACT above); 3: they differ
+  bool rb, dacc;
+};
+
+static BnFeatures bn_features(const BnMulti& m) {
+  BnFeatures f{-1, false, false};
+  for (int j = 0; j < m.n; ++j) {
+    const BnLayer& L = m.L[j];
+    const int a = !L.relu ? 0 : (L.mk ? 1 : (L.a ? 2 : 0));
+    f.act = f.act < 0 ? a : (f.act == a ? f.act : 3);
+    f.rb = f.rb || L.rx;
+    f.dacc = f.dacc || (L.dres && L.dres_acc);
+  }
+  if (f.act < 0) f.act = 3;
+  return f;
+}
+
+typedef void (*BnKernel)(BnMulti);
+constexpr BnKernel kBwdReduce[4][2] = {  // [act][rb]
+    {bn_bwd_reduce_multi_kernel<0, false>, bn_bwd_reduce_multi_kernel<0, true>},
+    {bn_bwd_reduce_multi_kernel<1, false>, bn_bwd_reduce_multi_kernel<1, true>},
+    {bn_bwd_reduce_multi_kernel<2, false>, bn_bwd_reduce_multi_kernel<2, true>},
+    {bn_bwd_reduce_multi_kernel<3, false>, bn_bwd_reduce_multi_kernel<3, true>}};
+constexpr BnKernel kBwdApply[4][2][2] = {  // [act][rb][dacc]
+    {{bn_bwd_apply_multi_kernel<0, false, false>, bn_bwd_apply_multi_kernel<0, false, true>},
+     {bn_bwd_apply_multi_kernel<0, true, false>, bn_bwd_apply_multi_kernel<0, true, true>}},
+    {{bn_bwd_apply_multi_kernel<1, false, false>, bn_bwd_apply_multi_kernel<1, false, true>},
+     {bn_bwd_apply_multi_kernel<1, true, false>, bn_bwd_apply_multi_kernel<1, true, true>}},
+    {{bn_bwd_apply_multi_kernel<2, false, false>, bn_bwd_apply_multi_kernel<2, false, true>},
+     {bn_bwd_apply_multi_kernel<2, true, false>, bn_bwd_apply_multi_kernel<2, true, true>}},
+    {{bn_bwd_apply_multi_kernel<3, false, false>, bn_bwd_apply_multi_kernel<3, false, true>},
+     {bn_bwd_apply_multi_kernel<3, true, false>, bn_bwd_apply_multi_kernel<3, true, true>}}};
 
 // One block per (layer, channel): reduce the layer's partial rows in double (fixed
 // order), then MODE 0: finalize (+ running statistics); MODE 1: sums + dgamma/dbeta
@@ -1296,61 +1252,35 @@ struct FinMulti {
   int n;
 };
 
-__device__ __forceinline__ void bn_finalize_channel(const FinLayer& L, int c, double s0,
-                                                    double s1) {
+__device__ __forceinline__ void bn_finalize_layer(const FinLayer& L, int c, double s0, double s1) {
   const double count = L.countp ? *L.countp : L.count;
   if (c == 0 && L.nbt) L.nbt[0] += 1;
-  const double mean = s0 / count;
-  double var = s1 / count - mean * mean;
-  if (var < 0.0) var = 0.0;
-  const double invstd = 1.0 / sqrt(var + (double)L.eps);
-  const float gm = L.gamma ? L.gamma[c] : 1.f;
-  const float bt = L.beta ? L.beta[c] : 0.f;
-  L.save[c] = (float)mean;
-  L.save[L.C + c] = (float)invstd;
-  L.save[2 * L.C + c] = (float)(gm * invstd);
-  L.save[3 * L.C + c] = (float)(bt - mean * (gm * invstd));
-  if (L.rmean) {
-    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    L.rmean[c] = (float)((1.0 - L.momentum) * L.rmean[c] + L.momentum * mean);
-    L.rvar[c] = (float)((1.0 - L.momentum) * L.rvar[c] + L.momentum * unbiased);
-  }
+  bn_finalize_channel<false>(L, c, s0, s1, count);
 }
 
 template <int MODE>
 __global__ __launch_bounds__(256) void reduce_then_multi_kernel(FinMulti m) {
-  __shared__ double red[2][4];
   int i = 0;
   while (i + 1 < m.n && (int)blockIdx.x >= m.L[i + 1].blk0) ++i;
   const FinLayer& L = m.L[i];
   const int c = blockIdx.x - L.blk0;
-  const int tid = threadIdx.x;
-  double a = 0.0, b = 0.0;
-  rows_sum2(L.part, L.rows, L.C, c, tid, a, b);
-  a = wave_sum_d(a);
-  b = wave_sum_d(b);
-  if ((tid & 63) == 0) {
-    red[0][tid >> 6] = a;
-    red[1][tid >> 6] = b;
-  }
-  __syncthreads();
-  if (tid != 0) return;
-  const double s0 = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-  const double s1 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+  double s0 = 0.0, s1 = 0.0;
+  rows_sum2(L.part, L.rows, L.C, c, threadIdx.x, s0, s1);
+  if (!block_sum_d(s0, s1)) return;
   L.sums[c] = s0;
   L.sums[L.C + c] = s1;
   if (MODE == 1) {
     if (L.dgamma) L.dgamma[c] += (float)s1;
     if (L.dbeta) L.dbeta[c] += (float)s0;
   } else if (MODE == 0) {
-    bn_finalize_channel(L, c, s0, s1);
+    bn_finalize_layer(L, c, s0, s1);
   }
 }
 
 // From (all-reduced) sums: one block per layer, threads over channels.
 __global__ __launch_bounds__(256) void bn_finalize_multi_kernel(FinMulti m) {
   const FinLayer& L = m.L[blockIdx.x];
-  for (int c = threadIdx.x; c < L.C; c += 256) bn_finalize_channel(L, c, L.sums[c], L.sums[L.C + c]);
+  for (int c = threadIdx.x; c < L.C; c += 256) bn_finalize_layer(L, c, L.sums[c], L.sums[L.C + c]);
 }
 
 static bool v4_ok(const void* p, int64_t ps) {
@@ -1406,18 +1336,51 @@ int vae2_bn_partials_reduce(const float* partials, int64_t rows, int64_t c,
   return check_launch(fn);
 }
 
+static const char* const kRunningPair = "running_mean and running_var must both be set or both be null";
+static bool running_pair_ok(const float* rm, const float* rv) { return (rm == nullptr) == (rv == nullptr); }
+
+// vae2_bn_finalize / _shifted (mean_shift null: unshifted)
+static int bn_finalize(const char* fn, const double* sums, double count, const float* mean_shift,
+                       const float* gamma, const float* beta, float* running_mean,
+                       float* running_var, int64_t* num_batches_tracked, float momentum,
+                       float eps, int64_t c, float* save, void* stream) {
+  VAE2_REQUIRE(sums && save && c > 0 && count > 0, fn, "bad arguments");
+  VAE2_REQUIRE(running_pair_ok(running_mean, running_var), fn, kRunningPair);
+  VAE2_LAUNCH(bn_finalize_kernel, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0,
+              as_stream(stream), sums, count, gamma, beta, running_mean, running_var,
+              num_batches_tracked, momentum, eps, c, save, mean_shift);
+  return check_launch(fn);
+}
+
+// vae2_bn_reduce_finalize / _shifted
+static int bn_reduce_finalize(const char* fn, const float* partials, int64_t rows, int64_t c,
+                              double* sums, double count, const float* mean_shift,
+                              const float* gamma, const float* beta, float* running_mean,
+                              float* running_var, int64_t* num_batches_tracked, float momentum,
+                              float eps, float* save, void* stream) {
+  VAE2_REQUIRE(partials && sums && save && rows > 0 && c > 0 && count > 0, fn, "bad arguments");
+  VAE2_REQUIRE(running_pair_ok(running_mean, running_var), fn, kRunningPair);
+  VAE2_LAUNCH((reduce_then_kernel<0>), dim3((unsigned)c), dim3(256), 0, as_stream(stream),
+              partials, rows, c, sums, count, gamma, beta, running_mean, running_var,
+              num_batches_tracked, momentum, eps, save, (float*)nullptr, (float*)nullptr,
+              mean_shift);
+  return check_launch(fn);
+}
+
 int vae2_bn_finalize(const double* sums, double count, const float* gamma,
                      const float* beta, float* running_mean, float* running_var,
                      int64_t* num_batches_tracked, float momentum, float eps,
                      int64_t c, float* save, void* stream) {
-  const char* fn = "vae2_bn_finalize";
-  VAE2_REQUIRE(sums && save && c > 0 && count > 0, fn, "bad arguments");
-  VAE2_REQUIRE((running_mean == nullptr) == (running_var == nullptr), fn,
-               "running_mean and running_var must both be set or both be null");
-  VAE2_LAUNCH(bn_finalize_kernel, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0,
-                     as_stream(stream), sums, count, gamma, beta, running_mean,
-                     running_var, num_batches_tracked, momentum, eps, c, save);
-  return check_launch(fn);
+  return bn_finalize("vae2_bn_finalize", sums, count, nullptr, gamma, beta, running_mean,
+                     running_var, num_batches_tracked, momentum, eps, c, save, stream);
+}
+
+int vae2_bn_finalize_shifted(const double* sums, double count, const float* mean_shift,
+                             const float* gamma, const float* beta, float* running_mean,
+                             float* running_var, int64_t* num_batches_tracked, float momentum,
+                             float eps, int64_t c, float* save, void* stream) {
+  return bn_finalize("vae2_bn_finalize_shifted", sums, count, mean_shift, gamma, beta, running_mean,
+                     running_var, num_batches_tracked, momentum, eps, c, save, stream);
 }
 
 int vae2_bn_reduce_finalize(const float* partials, int64_t rows, int64_t c,
@@ -1425,14 +1388,9 @@ int vae2_bn_reduce_finalize(const float* partials, int64_t rows, int64_t c,
                             const float* beta, float* running_mean, float* running_var,
                             int64_t* num_batches_tracked, float momentum, float eps,
                             float* save, void* stream) {
-  const char* fn = "vae2_bn_reduce_finalize";
-  VAE2_REQUIRE(partials && sums && save && rows > 0 && c > 0 && count > 0, fn, "bad arguments");
-  VAE2_REQUIRE((running_mean == nullptr) == (running_var == nullptr), fn,
-               "running_mean and running_var must both be set or both be null");
-  VAE2_LAUNCH((reduce_then_kernel<0>), dim3((unsigned)c), dim3(256), 0, as_stream(stream),
-                     partials, rows, c, sums, count, gamma, beta, running_mean, running_var,
-                     num_batches_tracked, momentum, eps, save, (float*)nullptr, (float*)nullptr);
-  return check_launch(fn);
+  return bn_reduce_finalize("vae2_bn_reduce_finalize", partials, rows, c, sums, count, nullptr,
+                            gamma, beta, running_mean, running_var, num_batches_tracked,
+                            momentum, eps, save, stream);
 }
 
 int vae2_bn_reduce_finalize_shifted(const float* partials, int64_t rows, int64_t c,
@@ -1441,29 +1399,9 @@ int vae2_bn_reduce_finalize_shifted(const float* partials, int64_t rows, int64_t
                                     float* running_mean, float* running_var,
                                     int64_t* num_batches_tracked, float momentum, float eps,
                                     float* save, void* stream) {
-  const char* fn = "vae2_bn_reduce_finalize_shifted";
-  VAE2_REQUIRE(partials && sums && save && rows > 0 && c > 0 && count > 0, fn, "bad arguments");
-  VAE2_REQUIRE((running_mean == nullptr) == (running_var == nullptr), fn,
-               "running_mean and running_var must both be set or both be null");
-  VAE2_LAUNCH((reduce_then_kernel<0>), dim3((unsigned)c), dim3(256), 0, as_stream(stream),
-              partials, rows, c, sums, count, gamma, beta, running_mean, running_var,
-              num_batches_tracked, momentum, eps, save, (float*)nullptr, (float*)nullptr,
-              mean_shift);
-  return check_launch(fn);
-}
-
-int vae2_bn_finalize_shifted(const double* sums, double count, const float* mean_shift,
-                             const float* gamma, const float* beta, float* running_mean,
-                             float* running_var, int64_t* num_batches_tracked, float momentum,
-                             float eps, int64_t c, float* save, void* stream) {
-  const char* fn = "vae2_bn_finalize_shifted";
-  VAE2_REQUIRE(sums && save && c > 0 && count > 0, fn, "bad arguments");
-  VAE2_REQUIRE((running_mean == nullptr) == (running_var == nullptr), fn,
-               "running_mean and running_var must both be set or both be null");
-  VAE2_LAUNCH(bn_finalize_kernel, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0,
-              as_stream(stream), sums, count, gamma, beta, running_mean, running_var,
-              num_batches_tracked, momentum, eps, c, save, mean_shift);
-  return check_launch(fn);
+  return bn_reduce_finalize("vae2_bn_reduce_finalize_shifted", partials, rows, c, sums, count,
+                            mean_shift, gamma, beta, running_mean, running_var,
+                            num_batches_tracked, momentum, eps, save, stream);
 }
 
 int vae2_bn_bwd_reduce_param_grads(const float* partials, int64_t rows, int64_t c,
@@ -1493,8 +1431,7 @@ int vae2_bn_apply(const float* x, const vae2_act* xd, const float* save,
                   const vae2_act* yd, int relu, void* stream) {
   const char* fn = "vae2_bn_apply";
   VAE2_REQUIRE(x && save && y && act_ok(xd) && act_ok(yd), fn, "bad arguments");
-  VAE2_REQUIRE(xd->n == yd->n && xd->h == yd->h && xd->w == yd->w && xd->c == yd->c, fn,
-               "x / y shape mismatch");
+  VAE2_REQUIRE(same_shape(xd, yd), fn, "x / y shape mismatch");
   Act r = to_act(yd);
   if (res) {
     VAE2_REQUIRE(act_ok(rd) && same_shape(rd, xd), fn, "residual shape mismatch");
@@ -1598,30 +1535,66 @@ int vae2_bn_relu_bwd_apply(const float* dy, const vae2_act* dyd, const float* y,
 // ------------------------------------------------- multi-layer launchers ----
 static bool bn_layer_quad_ok(const vae2_bn_layer& l, bool bwd) {
   const vae2_act& x = l.xd;
+  // an operand of the quad path: aligned, and of x's pixels and channels
+  auto like_x = [&](const void* p, const vae2_act& d) { return v4_ok(p, d.ps) && same_shape(&d, &x); };
   if (!l.x || !l.o || !l.save || !act_ok(&x) || !quad_ok(x.c) || !v4_ok(l.x, x.ps)) return false;
-  if (!v4_ok(l.o, l.od.ps) || l.od.n != x.n || l.od.h != x.h || l.od.w != x.w || l.od.c != x.c)
-    return false;
-  if (l.a && (!v4_ok(l.a, l.ad.ps) || l.ad.n != x.n || l.ad.h != x.h || l.ad.w != x.w ||
-              l.ad.c < x.c))
-    return false;
+  if (!like_x(l.o, l.od)) return false;
+  if (l.a && (!v4_ok(l.a, l.ad.ps) || !same_nhw(&l.ad, &x) || l.ad.c < x.c)) return false;
   if (bwd) {
-    if (!l.dy || !v4_ok(l.dy, l.dyd.ps) || l.dyd.n != x.n || l.dyd.h != x.h || l.dyd.w != x.w ||
-        l.dyd.c != x.c)
-      return false;
-    if (l.dres && (!v4_ok(l.dres, l.dresd.ps) || l.dresd.c != x.c || l.dresd.n != x.n ||
-                   l.dresd.h != x.h || l.dresd.w != x.w))
-      return false;
+    if (!l.dy || !like_x(l.dy, l.dyd)) return false;
+    if (l.dres && !like_x(l.dres, l.dresd)) return false;
   }
   if (l.rx) {  // the residual BN's input (and its gradient): same pixels and channels
-    const vae2_act& r = l.rxd;
-    if (!l.rsave || !v4_ok(l.rx, r.ps) || r.n != x.n || r.h != x.h || r.w != x.w || r.c != x.c)
-      return false;
+    if (!l.rsave || !like_x(l.rx, l.rxd)) return false;
     if (!bwd && l.a) return false;  // one residual: stored (a) or through its BN (rx)
-    if (bwd && (l.dres || !l.rdx || !v4_ok(l.rdx, l.rdxd.ps) || l.rdxd.c != x.c ||
-                l.rdxd.n != x.n || l.rdxd.h != x.h || l.rdxd.w != x.w))
-      return false;
+    if (bwd && (l.dres || !l.rdx || !like_x(l.rdx, l.rdxd))) return false;
   }
   return act_pixels(&x) * x.c < (int64_t(1) << 31);
+}
+
+// Layers ls[0 .. cnt) as one launch: the device records, each layer's first block, m.total
+// blocks; m.v2 cleared when an extent does not fit the buffer bodies' 32-bit byte offsets.
+static void bn_multi_pack(const vae2_bn_layer* ls, int cnt, int kind, BnMulti& m) {
+  m = BnMulti{};
+  m.n = cnt;
+  m.v2 = g_bn_v2;
+  for (int j = 0; j < cnt; ++j) {
+    const vae2_bn_layer& l = ls[j];
+    BnLayer& L = m.L[j];
+    L.x = l.x; L.a = l.a; L.o = l.o; L.dy = l.dy; L.dres = l.dres; L.part = l.partials;
+    L.save = l.save; L.gamma = l.gamma; L.sums = l.sums; L.countp = l.countp;
+    L.count = l.count;
+    L.P = act_pixels(&l.xd);
+    L.C = (int)l.xd.c;
+    L.x_ps = (int)l.xd.ps; L.a_ps = (int)l.ad.ps; L.o_ps = (int)l.od.ps;
+    L.dy_ps = (int)l.dyd.ps; L.dres_ps = (int)l.dresd.ps;
+    L.dres_acc = l.dres_acc;
+    L.relu = l.relu;
+    L.rx = l.rx; L.rsave = l.rsave; L.rgamma = l.rgamma; L.rpart = l.rpartials;
+    L.rsums = l.rsums; L.rdx = l.rdx;
+    L.rx_ps = (int)l.rxd.ps; L.rdx_ps = (int)l.rdxd.ps;
+    L.mk = l.mask;
+    L.rows = quad_rows(l.xd.c);
+    L.blk0 = m.total;
+    if (kind == 1) {
+      L.ppb = pix_per_block(L.P, L.C);
+      m.total += (int)ceil_div(L.P, L.ppb);
+    } else {
+      m.total += (int)ceil_div(L.P, (int64_t)L.rows * kApplyU);
+    }
+    const int64_t ext = L.P * std::max({l.xd.ps, l.od.ps, l.dyd.ps, l.ad.ps, l.dresd.ps,
+                                        l.rxd.ps, l.rdxd.ps, (int64_t)1}) * 4;
+    if (ext >= (int64_t(1) << 31)) m.v2 = 0;
+  }
+}
+
+// The kernel of a launch.  Tune key 8 = 0 and an extent of 2 GB or more both clear m.v2: the
+// same bodies over PtrMem (one all-features instance each).
+static BnKernel bn_multi_pick(const BnMulti& m, int kind) {
+  if (kind == 0) return m.v2 ? bn_apply_multi_kernel : bn_apply_multi_r4_kernel;
+  const BnFeatures f = bn_features(m);
+  if (kind == 1) return m.v2 ? kBwdReduce[f.act][f.rb] : bn_bwd_reduce_multi_r4_kernel;
+  return m.v2 ? kBwdApply[f.act][f.rb][f.dacc] : bn_bwd_apply_multi_r4_kernel;
 }
 
 // kind 0: forward apply, 1: backward reduce, 2: backward apply
@@ -1640,61 +1613,16 @@ static int bn_multi_launch(int n, const vae2_bn_layer* ls, int kind, void* strea
     VAE2_REQUIRE(kind != 2 || l.countp || l.count > 0, fn, "bad count");
   }
   for (int i0 = 0; i0 < n; i0 += kBnMaxLayers) {
-    BnMulti m{};
-    m.n = n - i0 < kBnMaxLayers ? n - i0 : kBnMaxLayers;
-    int blocks = 0;
-    for (int j = 0; j < m.n; ++j) {
-      const vae2_bn_layer& l = ls[i0 + j];
-      BnLayer& L = m.L[j];
-      L.x = l.x; L.a = l.a; L.o = l.o; L.dy = l.dy; L.dres = l.dres; L.part = l.partials;
-      L.save = l.save; L.gamma = l.gamma; L.sums = l.sums; L.countp = l.countp;
-      L.count = l.count;
-      L.P = act_pixels(&l.xd);
-      L.C = (int)l.xd.c;
-      L.x_ps = (int)l.xd.ps; L.a_ps = (int)l.ad.ps; L.o_ps = (int)l.od.ps;
-      L.dy_ps = (int)l.dyd.ps; L.dres_ps = (int)l.dresd.ps;
-      L.dres_acc = l.dres_acc;
-      L.relu = l.relu;
-      L.rx = l.rx; L.rsave = l.rsave; L.rgamma = l.rgamma; L.rpart = l.rpartials;
-      L.rsums = l.rsums; L.rdx = l.rdx;
-      L.rx_ps = (int)l.rxd.ps; L.rdx_ps = (int)l.rdxd.ps;
-      L.mk = l.mask;
-      L.rows = quad_rows(l.xd.c);
-      L.blk0 = blocks;
-      if (kind == 1) {
-        L.ppb = pix_per_block(L.P, L.C);
-        blocks += (int)ceil_div(L.P, L.ppb);
-      } else {
-        blocks += (int)ceil_div(L.P, (int64_t)L.rows * kApplyU);
-      }
-    }
-    if (blocks == 0) continue;
-    m.v2 = g_bn_v2;
-    m.total = blocks;
-    for (int j = 0; j < m.n; ++j) {  // 32-bit buffer offsets: every extent below 2 GB
-      const vae2_bn_layer& l = ls[i0 + j];
-      const int64_t P = act_pixels(&l.xd);
-      const int64_t ext = P * std::max({l.xd.ps, l.od.ps, l.dyd.ps, l.ad.ps, l.dresd.ps,
-                                        l.rxd.ps, l.rdxd.ps, (int64_t)1}) * 4;
-      if (ext >= (int64_t(1) << 31)) m.v2 = 0;
-    }
-    hipStream_t st = as_stream(stream);
+    BnMulti m;
+    bn_multi_pack(ls + i0, n - i0 < kBnMaxLayers ? n - i0 : kBnMaxLayers, kind, m);
+    if (m.total == 0) continue;
+    int blocks = m.total;
     if (kind != 1 && m.v2 && g_bn_apply_res > 0 && blocks > g_bn_apply_res) {
       const int rounds = (blocks + g_bn_apply_res - 1) / g_bn_apply_res;
       blocks = (blocks + rounds - 1) / rounds;  // (m.total keeps the chunk count)
     }
-    if (kind == 0 && m.v2)
-      VAE2_LAUNCH(bn_apply_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, st, m);
-    else if (kind == 0)
-      VAE2_LAUNCH(bn_apply_multi_r4_kernel, dim3((unsigned)blocks), dim3(256), 0, st, m);
-    else if (kind == 1 && m.v2)
-      bwd_reduce_launch(m, (unsigned)blocks, st);
-    else if (kind == 1)
-      VAE2_LAUNCH(bn_bwd_reduce_multi_r4_kernel, dim3((unsigned)blocks), dim3(256), 0, st, m);
-    else if (m.v2)
-      bwd_apply_launch(m, (unsigned)blocks, st);
-    else
-      VAE2_LAUNCH(bn_bwd_apply_multi_r4_kernel, dim3((unsigned)blocks), dim3(256), 0, st, m);
+    const BnKernel k = bn_multi_pick(m, kind);
+    VAE2_LAUNCH(k, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), m);
     const int rc = check_launch(fn);
     if (rc) return rc;
   }
@@ -1740,8 +1668,7 @@ int vae2_bn_multi_reduce(int n, const vae2_bn_fin* fins, int mode, void* stream)
     const vae2_bn_fin& f = fins[i];
     VAE2_REQUIRE(f.partials && f.rows > 0, fn, "missing partials");
     VAE2_REQUIRE(mode != 0 || (f.save && (f.countp || f.count > 0)), fn, "missing save / count");
-    VAE2_REQUIRE((f.running_mean == nullptr) == (f.running_var == nullptr), fn,
-                 "running_mean and running_var must both be set or both be null");
+    VAE2_REQUIRE(running_pair_ok(f.running_mean, f.running_var), fn, kRunningPair);
   }
   for (int i0 = 0; i0 < n; i0 += kBnMaxLayers) {
     FinMulti m;
