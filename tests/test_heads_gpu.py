@@ -155,49 +155,80 @@ def test_upsample_adjoint_streaming_equals_lane_kernel(hw, n):
         assert max_rel(a, b) < 1e-6, max_rel(a, b)
 
 
-@pytest.mark.parametrize("n,c,H,W,nsrc", [(2, 270, 64, 128, 3), (1, 70, 8, 64, 3),
-                                          (1, 18, 96, 192, 3), (2, 36, 40, 128, 2),
-                                          (1, 20, 34, 64, 1), (3, 64, 32, 64, 3)])
-def test_upsample_adjoint_multi_against_fp64(n, c, H, W, nsrc):
+CEIL_HALVING = ((5, 11), (3, 6), (2, 3))  # targets of a (10, 22) dy, as stride-2 convs produce
+# max_rel of that case against fp64, measured with the library as it was before the adjoints
+# moved to upadj.hip (per target 8.560e-08, 2.905e-07, 1.848e-07; the same at every algo)
+GENERIC_MAX_REL = 2.905e-07
+
+
+def _adjoint_case(n, c, H, W, tgt):
+    """dy in fp64 and on the device, plus the target sizes: `tgt` is either a count of exact
+    2 / 4 / 8 downsamplings or the explicit (h, w) list."""
+    from vae2 import ops
+    sizes = ([(H >> (s + 1), W >> (s + 1)) for s in range(tgt)] if isinstance(tgt, int)
+             else list(tgt))
+    g = torch.Generator().manual_seed(H * W + c)
+    dy = torch.randn(n, c, H, W, generator=g, dtype=torch.float64)
+    gt = ops.new_act((n, H, W, c), torch.empty(0, device=DEV))
+    gt.copy_(dy.float().permute(0, 2, 3, 1))
+    return dy, gt, sizes
+
+
+def _adjoint_targets(gt, n, c, sizes):
+    """NaN-filled targets (every element must be written) and their C-ABI arrays."""
+    import ctypes
+    from vae2 import ops
+    from vae2._lib import Act
+    dxs = [ops.new_act((n, h, w, c), gt) for h, w in sizes]
+    for d in dxs:
+        d.fill_(float("nan"))
+    views = [ops.act_of(d) for d in dxs]
+    acts = (Act * 3)(*[a for _, a in views])
+    ptrs = (ctypes.c_void_p * 3)(*[p for p, _ in views])
+    return dxs, ptrs, acts
+
+
+@pytest.mark.parametrize("n,c,H,W,tgt", [
+    (2, 270, 64, 128, 3), (1, 70, 8, 64, 3), (1, 18, 96, 192, 3), (2, 36, 40, 128, 2),
+    (1, 20, 34, 64, 1), (3, 64, 32, 64, 3),
+    pytest.param(1, 5, 10, 22, CEIL_HALVING, id="1-5-10-22-ceil_halving")])
+def test_upsample_adjoint_multi_against_fp64(n, c, H, W, tgt):
     """vae2_upsample_bilinear_bwd_multi (the heads' dL/dz_j = up_j^T(dL/dy)) against
     torch's fp64 autograd of F.interpolate(bilinear, align_corners=False)
     (enc_hrnet.py:839-845): the one-pass band kernel at its default and at 8 / 64 dy rows
     per workgroup, and the two-pass form (vae2_heads_set_algo bit 2).  Shapes cover one
     band, several bands, a last band shorter than the others, 1-row coarsest targets (both
-    vertical folds in one row) and pad channels (c % 64 != 0)."""
+    vertical folds in one row) and pad channels (c % 64 != 0).  The last case's targets are
+    no exact halvings: it runs the generic table kernels (up_adj_h / up_adj_v) at every
+    algo."""
     import ctypes
     from vae2 import _lib, ops
-    from vae2._lib import Act, call
+    from vae2._lib import call
     lib = _lib.load()
-    g = torch.Generator().manual_seed(H * W + c)
-    dy = torch.randn(n, c, H, W, generator=g, dtype=torch.float64)
+    dy, gt, sizes = _adjoint_case(n, c, H, W, tgt)
     refs = []
-    for s in range(nsrc):
-        z = torch.zeros(n, c, H >> (s + 1), W >> (s + 1), dtype=torch.float64,
-                        requires_grad=True)
+    for h, w in sizes:
+        z = torch.zeros(n, c, h, w, dtype=torch.float64, requires_grad=True)
         F.interpolate(z, size=(H, W), mode="bilinear", align_corners=False).backward(dy)
         refs.append(z.grad)
-    gt = ops.new_act((n, H, W, c), torch.empty(0, device=DEV))
-    gt.copy_(dy.float().permute(0, 2, 3, 1))
+    # Exact 2^k ratios have exact fp32 weights: 2e-6.  The generic route rounds its weights
+    # (lerp_index in fp32): 4 x the measured GENERIC_MAX_REL = 1.162e-06, the margin for the
+    # rounding-order noise of lerp_index.
+    bound = 2e-6 if isinstance(tgt, int) else 4 * GENERIC_MAX_REL
     gp, ga = ops.act_of(gt)
     try:
         for algo in (0, 8 << 8, 64 << 8, 4):
             lib.vae2_heads_set_algo(algo)
-            dxs = [ops.new_act((n, H >> (s + 1), W >> (s + 1), c), gt) for s in range(nsrc)]
-            for d in dxs:
-                d.fill_(float("nan"))  # every target element must be written
-            views = [ops.act_of(d) for d in dxs]
-            acts = (Act * 3)(*[a for _, a in views])
-            ptrs = (ctypes.c_void_p * 3)(*[p for p, _ in views])
-            wsz = lib.vae2_upsample_bilinear_bwd_multi_ws_size(ctypes.byref(ga), nsrc, acts)
+            dxs, ptrs, acts = _adjoint_targets(gt, n, c, sizes)
+            wsz = lib.vae2_upsample_bilinear_bwd_multi_ws_size(ctypes.byref(ga), len(sizes), acts)
             ws = torch.empty(max(wsz, 1), device=DEV)
-            call("vae2_upsample_bilinear_bwd_multi", gp, ctypes.byref(ga), nsrc, ptrs, acts,
-                 ws.data_ptr(), wsz, None)
+            call("vae2_upsample_bilinear_bwd_multi", gp, ctypes.byref(ga), len(sizes), ptrs,
+                 acts, ws.data_ptr(), wsz, None)
             torch.cuda.synchronize()
             for d, r in zip(dxs, refs):
                 got = d.permute(0, 3, 1, 2).double().cpu()
                 assert torch.isfinite(got).all(), algo
-                assert max_rel(got, r) < 2e-6, (algo, max_rel(got, r))
+                assert max_rel(got, r) < bound, (algo, max_rel(got, r))
     finally:
         lib.vae2_heads_set_algo(0)
 
@@ -258,4 +289,71 @@ def test_upsum_one_pass_against_fp64(n, H, W, cin, nup):
             assert max_rel(st[0], s1) < 1e-4, (algo, max_rel(st[0], s1))
             assert max_rel(st[1], s2) < 1e-5, (algo, max_rel(st[1], s2))
     finally:
+        lib.vae2_heads_set_algo(0)
+
+
+@pytest.mark.parametrize("v", [1 << b for b in range(8)] + [8 << 8, 64 << 8,
+                                                            1 | 8 | 32 | 128 | (16 << 8)])
+def test_heads_set_algo_round_trip(v):
+    """vae2_heads_set_algo returns the value it replaces: every switch bit and band byte
+    reads back as it was set."""
+    from vae2 import _lib
+    lib = _lib.load()
+    try:
+        lib.vae2_heads_set_algo(v)
+        assert lib.vae2_heads_set_algo(0) == v
+    finally:
+        lib.vae2_heads_set_algo(0)
+
+
+@pytest.mark.parametrize("band", [12, 4, 7])
+def test_heads_set_algo_refused_band_reads_back_default(band):
+    """A band that is below 8 or no multiple of 8 leaves the default (32 rows), which reads
+    back as 0 in the band byte; the switch bits beside it are still taken."""
+    from vae2 import _lib
+    lib = _lib.load()
+    try:
+        lib.vae2_heads_set_algo((band << 8) | 4)
+        assert lib.vae2_heads_set_algo(0) == 4
+    finally:
+        lib.vae2_heads_set_algo(0)
+
+
+@pytest.mark.parametrize("n,c,H,W,tgt,algo", [
+    pytest.param(1, 18, 16, 64, 3, 0, id="one_pass"),
+    pytest.param(1, 18, 16, 64, 3, 4, id="pow2_two_pass"),
+    pytest.param(1, 5, 10, 22, CEIL_HALVING, 0, id="generic")])
+def test_upsample_adjoint_multi_workspace_agrees_with_launcher(n, c, H, W, tgt, algo):
+    """The size vae2_upsample_bilinear_bwd_multi_ws_size reports is what the launcher of the
+    same route uses: with exactly that size every target element is written and nothing
+    behind the workspace is touched; one float less is refused before any launch."""
+    import ctypes
+    from vae2 import _lib, ops
+    from vae2._lib import HipError, call
+    lib = _lib.load()
+    _, gt, sizes = _adjoint_case(n, c, H, W, tgt)
+    gp, ga = ops.act_of(gt)
+    guard, sentinel = 1024, -12345.5
+    try:
+        lib.vae2_heads_set_algo(algo)
+        dxs, ptrs, acts = _adjoint_targets(gt, n, c, sizes)
+        wsz = lib.vae2_upsample_bilinear_bwd_multi_ws_size(ctypes.byref(ga), len(sizes), acts)
+        assert wsz >= 1
+        assert (wsz == 1) == (algo == 0 and isinstance(tgt, int))  # only one-pass needs none
+        ws = torch.full((wsz + guard,), float("nan"), device=DEV)
+        ws[wsz:] = sentinel
+        if wsz > 1:
+            lib.vae2_kernel_log(1)
+            with pytest.raises(HipError, match="workspace too small"):
+                call("vae2_upsample_bilinear_bwd_multi", gp, ctypes.byref(ga), len(sizes), ptrs,
+                     acts, ws.data_ptr(), wsz - 1, None)
+            assert lib.vae2_kernel_log_read(None, 0) == 0  # refused before any launch
+        call("vae2_upsample_bilinear_bwd_multi", gp, ctypes.byref(ga), len(sizes), ptrs, acts,
+             ws.data_ptr(), wsz, None)
+        torch.cuda.synchronize()
+        assert bool((ws[wsz:] == sentinel).all())
+        for d in dxs:
+            assert torch.isfinite(d).all()
+    finally:
+        lib.vae2_kernel_log(0)
         lib.vae2_heads_set_algo(0)

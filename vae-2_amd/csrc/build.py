@@ -18,9 +18,10 @@ DEFS = os.environ.get("VAE2_DEFS", "").split()
 OUT = os.path.join(PKG, f"libvae2_hip_{TAG}.so" if TAG else "libvae2_hip.so")
 BUILD = os.path.join(HERE, f"build_{TAG}" if TAG else "build")
 CONV = ["conv.hip", "conv_gather.hip", "conv_direct.hip", "conv_wgrad.hip"]
-SOURCES = CONV + ["bn.hip", "resample.hip", "elbo.hip", "heads.hip", "clips.hip", "metrics.hip",
-                  "wgrad_narrow.hip", "syncbn.hip", "dconv_stream.hip", "ssim_loss.hip"]
-HEADERS = ["common.h", "conv.h", os.path.join("..", "..", "include", "vae2_hip.h")]
+SOURCES = CONV + ["bn.hip", "resample.hip", "elbo.hip", "heads.hip", "upadj.hip", "runtime.hip",
+                  "clips.hip", "metrics.hip", "wgrad_narrow.hip", "syncbn.hip",
+                  "dconv_stream.hip", "ssim_loss.hip"]
+HEADERS = ["common.h", "conv.h", "heads.h", os.path.join("..", "..", "include", "vae2_hip.h")]
 ARCH = os.environ.get("VAE2_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
          "-Wno-unused-function", "-munsafe-fp-atomics"]

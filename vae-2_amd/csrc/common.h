@@ -225,12 +225,6 @@ __device__ constexpr float hat_w(int d, int f) {
   return 1.f - (float)(2 * d + 1 - f < 0 ? f - 1 - 2 * d : 2 * d + 1 - f) / (float)(2 * f);
 }
 
-// Internal (heads.hip): the fuse layers' pow2 upsampling adjoint through the one-pass
-// kernel, or -1 when its shape rules do not hold.
-int adj3_fuse_launch(const float* dy, const vae2_act* dyd, int n, float* const* dxs,
-                     const vae2_act* dxds, const float* betas, hipStream_t st);
-extern int g_relu_dual_q;  // heads.hip: vae2_heads_set_algo bit 7 clears it
-
 // Internal (wgrad_narrow.hip): the narrow-channel 3x3 weight gradient.  _splits: partial
 // slabs it writes for this layer (0: not handled); _launch: writes them into part
 // ([splits][cout][9 * cin4]) and returns their number, 0 when not handled, < 0 on error.

@@ -13,10 +13,9 @@
 //             apply:   dy = gamma*invstd*(g - mean(g) - xhat*mean(g*xhat)), sum_p dy (conv bias)
 // Each pass reads y once (16-byte NHWC quads); h and g are recomputed in registers.
 // Reductions are two-level with fixed orders (deterministic).
-#include "common.h"
+#include "heads.h"
 
 namespace vae2 {
-
 
 constexpr int kHeadMaxOut = 4;
 constexpr int64_t kHeadMaxPpb = 2048;  // pixels per block of the backward passes (LDS dout)
@@ -358,7 +357,7 @@ __global__ __launch_bounds__(256) void head_out_bwd_apply_kernel(
 // unconditional buffer loads, source columns clamped into the chunk's window), and the
 // epilogue adds the two horizontal taps per source and the bias, stores y and
 // accumulates the BN partial sums (written once per workgroup).
-constexpr int kUsXB = 64, kUsCB = 64, kUsMaxCin = 32;
+constexpr int kUsCB = 64, kUsMaxCin = 32;  // (kUsXB, the 64-pixel chunk: heads.h)
 // LDS column stride of source s's blended row: the epilogue's 4 lane groups read columns
 // 2 (s = 0), 1 (s = 1) or 0-1 (s = 2) apart, so stride * step = 16 (mod 32) puts each
 // 32-lane half of a ds_read_b32 on distinct banks.
@@ -721,534 +720,6 @@ __global__ __launch_bounds__(256) void upsum2_kernel(UpSum p) {
   }
 }
 
-// ------------------------------------------- upsampling adjoint, all sources ----
-// dx_s = up_s^T(dy) for every source s at once, separably.
-// Horizontal pass, workgroup = (dY row, 64-pixel chunk, 64-channel block): source
-// columns are partitioned between chunks (ix belongs to the chunk holding the output
-// coordinate of its centre), the chunk's dY pixels plus the interpolation halo are
-// staged in LDS once with per-pixel forward tables {i0, i1, l0, l1}, and each owned
-// column gathers hb_s[n][oy][ix][c] = sum_ox w(ox, ix) dy[n][oy][ox][c] from LDS.
-// Vertical pass, workgroup = (target row, 64-channel block): the row's weights are
-// tabulated once, then dx_s[n][iy][ix][c] = sum_oy w(oy, iy) hb_s[n][oy][ix][c].
-// The weights are exactly upsample_fwd_kernel's (lerp_index).  Lane = channel.
-struct UpAdj {
-  const float* dy;
-  int dy_ps, H, W, C;
-  float* hb[3];
-  float* dx[3];
-  int zh[3], zw[3], dx_ps[3];
-  float sh[3], sw[3];
-  int halo, nxb;
-  float beta[3];  // up_adj3_kernel: dx_s = adjoint + beta_s * dx_s (the fuse adjoints)
-};
-
-__device__ __forceinline__ void adj_window(int i, int in_size, int out_size, float scale,
-                                           int& lo, int& hi) {
-  lo = (int)floorf(((float)i - 0.5f) / scale - 0.5f) - 1;
-  hi = (int)ceilf(((float)i + 1.5f) / scale - 0.5f) + 1;
-  if (lo < 0) lo = 0;
-  if (hi > out_size - 1) hi = out_size - 1;
-  if (i == in_size - 1) hi = out_size - 1;  // clamped sources beyond the last input
-}
-
-// First source column owned by chunk xb (monotone in xb; xb = nxb gives zw).
-__device__ __forceinline__ int adj_owned_begin(int xb, int nxb, int zw, float sw) {
-  if (xb >= nxb) return zw;
-  if (xb <= 0) return 0;
-  int b = (int)ceilf(((float)(xb * kUsXB) + 0.5f) * sw - 0.5f);
-  return b < 0 ? 0 : (b > zw ? zw : b);
-}
-
-template <int NUP>
-__global__ __launch_bounds__(256) void up_adj_h_kernel(UpAdj p) {
-  extern __shared__ __attribute__((aligned(16))) float asm_[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int ncb = (p.C + 63) / 64;
-  const int xb = blockIdx.x % p.nxb;
-  const int cbi = (blockIdx.x / p.nxb) % ncb;
-  const int row = blockIdx.x / (p.nxb * ncb);  // n*H + oy
-  const int span = kUsXB + 2 * p.halo;
-  f4* tab = reinterpret_cast<f4*>(asm_);              // [NUP][span]
-  float* st = asm_ + 4 * NUP * span;                  // [span][64]
-  int ib[3], ie[3], wlo = 1 << 30, whi = -1;
-#pragma unroll
-  for (int s = 0; s < NUP; ++s) {
-    ib[s] = adj_owned_begin(xb, p.nxb, p.zw[s], p.sw[s]);
-    ie[s] = adj_owned_begin(xb + 1, p.nxb, p.zw[s], p.sw[s]);
-    if (ie[s] > ib[s]) {
-      int lo, hi, lo2, hi2;
-      adj_window(ib[s], p.zw[s], p.W, p.sw[s], lo, hi);
-      adj_window(ie[s] - 1, p.zw[s], p.W, p.sw[s], lo2, hi2);
-      wlo = lo < wlo ? lo : wlo;
-      whi = hi2 > whi ? hi2 : whi;
-    }
-  }
-  if (whi < wlo) return;  // no owned columns (uniform over the workgroup)
-  const int cnt = whi - wlo + 1;  // <= span (host-sized halo)
-#pragma unroll
-  for (int s = 0; s < NUP; ++s) {
-    for (int i = threadIdx.x; i < cnt; i += 256) {
-      const Lerp lx = lerp_index(wlo + i, p.zw[s], p.sw[s]);
-      tab[s * span + i] = f4{__int_as_float(lx.i0), __int_as_float(lx.i1), lx.l0, lx.l1};
-    }
-  }
-  {
-    const int c = cbi * 64 + lane;
-    const bool cok = c < p.C;
-    const float* drow = p.dy + (int64_t)row * p.W * p.dy_ps + c;
-    {
-      constexpr int SU = 24;  // pixels per wave in flight (span <= 96: one round trip)
-      for (int i0 = wave; i0 < cnt; i0 += 4 * SU) {
-        float v[SU];
-#pragma unroll
-        for (int u = 0; u < SU; ++u) {
-          const int i = i0 + 4 * u;
-          v[u] = (cok && i < cnt) ? drow[(int64_t)(wlo + i) * p.dy_ps] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < SU; ++u) {
-          const int i = i0 + 4 * u;
-          if (i < cnt) st[i * 64 + lane] = v[u];
-        }
-      }
-    }
-    __syncthreads();
-    if (!cok) return;
-    // Work items: (source, half of its owned columns); wave w streams items w, w+4, ...
-    // Streaming: pixels ox ascend, so each ox adds l0 to column i0 and l1 to i1 in
-    // {i0, i0+1} with i0 non-decreasing; two running sums (columns cur, cur+1) are kept
-    // and column cur is final (stored) once i0 moves past it.
-    for (int item = wave; item < 2 * NUP; item += 4) {
-      const int s = item % NUP, half = item / NUP;
-      const int mid = ib[s] + (ie[s] - ib[s] + 1) / 2;
-      const int cb = half ? mid : ib[s], ce = half ? ie[s] : mid;
-      if (cb >= ce) continue;
-      int lo, hi, lo2, hi2;
-      adj_window(cb, p.zw[s], p.W, p.sw[s], lo, hi);
-      adj_window(ce - 1, p.zw[s], p.W, p.sw[s], lo2, hi2);
-      float* hrow = p.hb[s] + (int64_t)row * p.zw[s] * p.C + c;
-      const f4* ts = tab + s * span - wlo;
-      const float* sv = st - wlo * 64 + lane;
-      int cur = cb - 1;
-      float a0 = 0.f, a1 = 0.f;  // sums of columns cur, cur + 1
-      for (int ox = lo; ox <= hi2; ++ox) {
-        const f4 t = ts[ox];  // wave-uniform: moved to scalar registers
-        const int i0 = __builtin_amdgcn_readfirstlane(__float_as_int(t[0]));
-        const int i1 = __builtin_amdgcn_readfirstlane(__float_as_int(t[1]));
-        const float l0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t[2])));
-        const float l1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t[3])));
-        const float v = sv[ox * 64];
-        while (cur < i0) {  // wave-uniform
-          if (cur >= cb && cur < ce) hrow[(int64_t)cur * p.C] = a0;
-          a0 = a1;
-          a1 = 0.f;
-          ++cur;
-        }
-        // now i0 <= cur (i0 < cur only left of the owned range: not ours)
-        if (i0 == cur) a0 = __builtin_fmaf(l0, v, a0);
-        if (i1 == cur) a0 = __builtin_fmaf(l1, v, a0);
-        else if (i1 == cur + 1) a1 = __builtin_fmaf(l1, v, a1);
-      }
-      if (cur >= cb && cur < ce) hrow[(int64_t)cur * p.C] = a0;
-      if (cur + 1 >= cb && cur + 1 < ce) hrow[(int64_t)(cur + 1) * p.C] = a1;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void up_adj_v_kernel(UpAdj p, int s) {
-  __shared__ float wy[64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int row = blockIdx.x;  // n*zh + iy
-  const int n = row / p.zh[s], iy = row - n * p.zh[s];
-  const int c = blockIdx.y * 64 + lane;
-  int lo, hi;
-  adj_window(iy, p.zh[s], p.H, p.sh[s], lo, hi);
-  const int cnt = hi - lo + 1 < 64 ? hi - lo + 1 : 64;  // host guarantees <= 64
-  if (threadIdx.x < cnt) {
-    const Lerp ly = lerp_index(lo + threadIdx.x, p.zh[s], p.sh[s]);
-    wy[threadIdx.x] = (ly.i0 == iy ? ly.l0 : 0.f) + (ly.i1 == iy ? ly.l1 : 0.f);
-  }
-  __syncthreads();
-  if (c >= p.C) return;
-  const float* hb = p.hb[s] + ((int64_t)n * p.H + lo) * p.zw[s] * p.C + c;
-  float* out = p.dx[s] + (int64_t)row * p.zw[s] * p.dx_ps[s] + c;
-  const int64_t rs = (int64_t)p.zw[s] * p.C;
-  for (int ix = wave; ix < p.zw[s]; ix += 8) {
-    const bool two = ix + 4 < p.zw[s];
-    const float* h0 = hb + (int64_t)ix * p.C;
-    const float* h1 = hb + (int64_t)(two ? ix + 4 : ix) * p.C;
-    float acc0 = 0.f, acc1 = 0.f;
-#pragma unroll 4
-    for (int t = 0; t < cnt; ++t) {
-      acc0 = __builtin_fmaf(wy[t], h0[t * rs], acc0);
-      acc1 = __builtin_fmaf(wy[t], h1[t * rs], acc1);
-    }
-    out[(int64_t)ix * p.dx_ps[s]] = acc0;
-    if (two) out[(int64_t)(ix + 4) * p.dx_ps[s]] = acc1;
-  }
-}
-
-// Exact 2^(s+1) ratios: static stencils (hat_w, common.h).
-constexpr int kAdjHalo = 4;  // F/2 for F <= 8
-
-// Horizontal pass, workgroup = (dY row, 64-pixel chunk, 64-channel block); the chunk and a
-// 4-pixel halo are staged in LDS (lane = channel); wave w computes the owned source
-// columns j = w, w + 4, ... of every source with immediate LDS offsets.
-template <int NUP>
-__global__ __launch_bounds__(256) void up_adj2_h_kernel(UpAdj p) {
-  constexpr int SPAN = kUsXB + 2 * kAdjHalo, PER = SPAN / 4;
-  __shared__ float st[SPAN][64];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ncb = (p.C + 63) / 64;
-  const int xb = blockIdx.x % p.nxb;
-  const int cbi = (blockIdx.x / p.nxb) % ncb;
-  const int row = blockIdx.x / (p.nxb * ncb);  // n*H + oy
-  const int c = cbi * 64 + lane;
-  const bool cok = c < p.C;
-  const int x0 = xb * kUsXB;
-  const float* drow = p.dy + (int64_t)row * p.W * p.dy_ps + (cok ? c : 0);
-  float v[PER];
-#pragma unroll
-  for (int u = 0; u < PER; ++u) {
-    const int ox = x0 - kAdjHalo + wave + 4 * u;
-    v[u] = (cok && ox >= 0 && ox < p.W) ? drow[(int64_t)ox * p.dy_ps] : 0.f;
-  }
-#pragma unroll
-  for (int u = 0; u < PER; ++u) st[wave + 4 * u][lane] = v[u];
-  __syncthreads();
-  if (!cok) return;
-#pragma unroll
-  for (int s = 0; s < NUP; ++s) {
-    const int F = 2 << s, zw = p.zw[s];
-    const float* sw = &st[F * wave + kAdjHalo][lane];  // column j = wave: pixels F*wave + d
-    float* hrow = p.hb[s] + (int64_t)row * zw * p.C + c;
-#pragma unroll
-    for (int jj = 0; jj < kUsXB / (2 << s) / 4; ++jj) {
-      const int j = wave + 4 * jj, ix = x0 / F + j;
-      float acc = 0.f;
-#pragma unroll
-      for (int d = -(1 << s); d < 3 * (1 << s); ++d) acc += hat_w(d, F) * sw[(4 * F * jj + d) * 64];
-      if (ix == 0) {  // virtual column -1 (pixels d - F)
-#pragma unroll
-        for (int d = 2 << s; d < 3 * (1 << s); ++d) acc += hat_w(d, F) * sw[(d - F) * 64];
-      }
-      if (ix == zw - 1) {  // virtual column zw (pixels F*(j+1) + d)
-#pragma unroll
-        for (int d = -(1 << s); d < 0; ++d) acc += hat_w(d, F) * sw[(4 * F * jj + F + d) * 64];
-      }
-      hrow[(int64_t)ix * p.C] = acc;
-    }
-  }
-}
-
-// Vertical pass of source S (F = 2^(S+1)), workgroup = (target row, 64-channel block).
-template <int S>
-__global__ __launch_bounds__(256) void up_adj2_v_kernel(UpAdj p) {
-  constexpr int F = 2 << S, HF = 1 << S;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int row = blockIdx.x;  // n*zh + iy
-  const int zh = p.zh[S], zw = p.zw[S];
-  const int n = row / zh, iy = row - n * zh;
-  const int c = blockIdx.y * 64 + lane;
-  if (c >= p.C) return;
-  const int64_t rs = (int64_t)zw * p.C;
-  const float* hb = p.hb[S] + (int64_t)n * p.H * rs + c;
-  float* out = p.dx[S] + (int64_t)row * zw * p.dx_ps[S] + c;
-  const int oy0 = F * iy;
-  constexpr int U = 4;  // target columns per wave iteration (their loads in flight together)
-  constexpr int NT = 3 * F;  // 2F taps + the two edge folds (HF rows each)
-  for (int ix0 = wave; ix0 < zw; ix0 += 4 * U) {
-    float v[U][NT];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int ix = ix0 + 4 * u;
-      const float* h = hb + (int64_t)(ix < zw ? ix : zw - 1) * p.C;
-#pragma unroll
-      for (int d = -HF; d < 3 * HF; ++d) {
-        const int oy = oy0 + d;
-        v[u][d + HF] = (oy >= 0 && oy < p.H) ? h[(int64_t)oy * rs] : 0.f;
-      }
-#pragma unroll
-      for (int e = 0; e < HF; ++e) {  // edge folds: rows d - F (top, d = F + e), F*zh + d
-        v[u][2 * F + e] = iy == 0 ? h[(int64_t)e * rs] : 0.f;
-        v[u][2 * F + HF + e] = iy == zh - 1 ? h[(int64_t)(F * zh - HF + e) * rs] : 0.f;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int ix = ix0 + 4 * u;
-      if (ix >= zw) break;
-      float acc = 0.f;
-#pragma unroll
-      for (int d = -HF; d < 3 * HF; ++d) acc += hat_w(d, F) * v[u][d + HF];
-      if (iy == 0) {
-#pragma unroll
-        for (int e = 0; e < HF; ++e) acc += hat_w(F + e, F) * v[u][2 * F + e];
-      }
-      if (iy == zh - 1) {
-#pragma unroll
-        for (int e = 0; e < HF; ++e) acc += hat_w(e - HF, F) * v[u][2 * F + HF + e];
-      }
-      out[(int64_t)ix * p.dx_ps[S]] = acc;
-    }
-  }
-}
-
-// Streaming form of the vertical pass: it only mixes hb rows, and an hb row
-// (zw * C floats, ix-major) is contiguous, so thread = 4 consecutive floats of the row:
-// one 16-byte load per contributing row (2F taps, plus the edge folds on the first / last
-// target row: uniform per workgroup), the same weights and summation order as
-// up_adj2_v_kernel, then the 4 results go to (ix, c) = divmod(k, C) of the (possibly
-// channel-padded) dx layout.  Workgroup = (target row, slice of the row).  Needs
-// zw * C % 4 == 0 (16-byte aligned rows).
-static int g_adj_stream = 1;  // vae2_heads_set_algo bit 0 clears it
-static int g_upsum_tight = 1;  // vae2_heads_set_algo bit 1 clears it
-static int g_upsum_one = 1;    // vae2_heads_set_algo bit 3 clears it (upsum2_kernel)
-// vae2_heads_set_algo bit 6 sets it: the fuse adjoints (resample.hip) through the one-pass
-// band kernel -- off: with 18-72 channels a 64-lane channel block is mostly idle and the
-// step measured 851-853 vs 861-866 frames/s through the two-pass quad kernels (A/B, same box)
-int g_fuse_adj3 = 0;
-int g_relu_dual_q = 1;         // vae2_heads_set_algo bit 7 clears it (relu_bwd_dual quad form)
-static int g_head_red_u = 2;   // vae2_heads_set_algo bit 4: 4 pixels in flight (backward reduce)
-static int g_head_app_u = 2;   // vae2_heads_set_algo bit 5: 4 pixels in flight (backward apply)
-
-template <int S>
-__global__ __launch_bounds__(256) void up_adj2_vs_kernel(UpAdj p, FastDiv cdiv) {
-  constexpr int F = 2 << S, HF = 1 << S;
-  const int row = blockIdx.x;  // n*zh + iy
-  const int zh = p.zh[S], zw = p.zw[S];
-  const int n = row / zh, iy = row - n * zh;
-  const int64_t rs = (int64_t)zw * p.C;
-  const int nq = (int)(rs >> 2);
-  const float* hb = p.hb[S] + (int64_t)n * p.H * rs;
-  float* out = p.dx[S] + (int64_t)row * zw * p.dx_ps[S];
-  const int oy0 = F * iy;
-  const uint32_t C = (uint32_t)p.C, dps = (uint32_t)p.dx_ps[S];
-  for (int q = blockIdx.y * 256 + threadIdx.x; q < nq; q += gridDim.y * 256) {
-    const int64_t k4 = 4 * (int64_t)q;
-    f4 v[4 * HF];
-#pragma unroll
-    for (int d = -HF; d < 3 * HF; ++d) {
-      const int oy = oy0 + d;
-      v[d + HF] = (oy >= 0 && oy < p.H) ? *reinterpret_cast<const f4*>(hb + oy * rs + k4)
-                                        : f4{0.f, 0.f, 0.f, 0.f};
-    }
-    f4 acc = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int d = -HF; d < 3 * HF; ++d) acc += hat_w(d, F) * v[d + HF];
-    if (iy == 0) {
-#pragma unroll
-      for (int e = 0; e < HF; ++e)
-        acc += hat_w(F + e, F) * *reinterpret_cast<const f4*>(hb + e * rs + k4);
-    }
-    if (iy == zh - 1) {
-#pragma unroll
-      for (int e = 0; e < HF; ++e)
-        acc += hat_w(e - HF, F) *
-               *reinterpret_cast<const f4*>(hb + (int64_t)(F * zh - HF + e) * rs + k4);
-    }
-    uint32_t ix = cdiv.div((uint32_t)k4), c = (uint32_t)k4 - ix * C;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      out[(int64_t)ix * dps + c] = acc[i];
-      if (++c == C) { c = 0; ++ix; }
-    }
-  }
-}
-
-// One-pass form of the power-of-two adjoint: dx_s = V_s^T H_s^T dy for every source with
-// dy read once (plus a row halo) and no hb intermediate (the two-pass form above writes and
-// re-reads 1/2 + 1/4 + 1/8 of dy).  Workgroup = (image, band of `br` dy rows, 64-pixel
-// chunk, 64-channel block); lane = channel; wave w owns the source columns whose pixels
-// start in [x0 + 16w, x0 + 16w + 16): 16/F per source.  The band's dy rows plus HF_max rows
-// above and below stream through registers (the next row's loads in flight during the
-// current row's arithmetic).  A dy row oy feeds exactly two target rows of source s,
-// ih = (oy + HF) / F and ih - 1 (taps d = oy - F*ih and d + F); per source and owned column
-// two accumulators follow them, and a row is stored once oy has moved past it.  Virtual
-// rows / columns -1 and z are folded into 0 / z-1 as in up_adj2_h / up_adj2_vs, with the
-// same hat_w weights; interior outputs keep the two-pass summation order.
-static int g_adj_fused = 1;  // vae2_heads_set_algo bit 2 clears it
-static int g_adj_band = 32;  // dy rows per workgroup (a multiple of 8)
-
-// Logical block order with consecutive ids on one XCD (the hardware deals workgroups out
-// round-robin over the 8 XCDs): neighbouring chunks / bands share dy halo rows in that L2.
-__device__ __forceinline__ int xcd_remap_blocks(int orig, int n) {
-  const int q = n >> 3, rr = n & 7, x = orig & 7;
-  return (x < rr ? x * (q + 1) : rr * (q + 1) + (x - rr) * q) + (orig >> 3);
-}
-
-// Per-source state of up_adj3_kernel: the wave's 16/F owned columns in the two target rows
-// the current dy row feeds (lo = ih - 1, hi = ih), cur = ih.
-template <int S>
-struct Adj3Src {
-  static constexpr int F = 2 << S, HF = 1 << S, J = 8 >> S;
-  float lo[J], hi[J];
-  int cur;
-};
-
-template <int S>
-__device__ __forceinline__ void adj3_store(const Adj3Src<S>& a, const UpAdj& p, int n, int iy,
-                                           int b0, int b1, int px0, int c, bool cok) {
-  constexpr int F = Adj3Src<S>::F;
-  if (!cok || iy < b0 / F || iy >= b1 / F) return;
-  float* out = p.dx[S] + ((int64_t)n * p.zh[S] + iy) * p.zw[S] * p.dx_ps[S] + c;
-  const int ix0 = px0 / F;
-  const float beta = p.beta[S];
-  if (beta != 0.f) {
-    float old[Adj3Src<S>::J];
-#pragma unroll
-    for (int j = 0; j < Adj3Src<S>::J; ++j) old[j] = out[(int64_t)(ix0 + j) * p.dx_ps[S]];
-#pragma unroll
-    for (int j = 0; j < Adj3Src<S>::J; ++j)
-      out[(int64_t)(ix0 + j) * p.dx_ps[S]] = a.lo[j] + beta * old[j];
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < Adj3Src<S>::J; ++j) out[(int64_t)(ix0 + j) * p.dx_ps[S]] = a.lo[j];
-}
-
-// dy row oy (pixels px0 - HM + i in v[i]) into source S's accumulators.
-template <int S, int HM>
-__device__ __forceinline__ void adj3_row(Adj3Src<S>& a, const float* v, int oy, const UpAdj& p,
-                                         int n, int b0, int b1, int px0, int c, bool cok) {
-  constexpr int F = Adj3Src<S>::F, HF = Adj3Src<S>::HF, J = Adj3Src<S>::J;
-  const int ih = (oy + HF) >> (S + 1);
-  if (ih != a.cur) {  // target row cur - 1 is complete
-    adj3_store<S>(a, p, n, a.cur - 1, b0, b1, px0, c, cok);
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      a.lo[j] = a.hi[j];
-      a.hi[j] = 0.f;
-    }
-    a.cur = ih;
-  }
-  const int d = oy - F * ih;
-  const float wh = hat_w(d, F), wl = hat_w(d + F, F);
-  const int zw = p.zw[S], ix0 = px0 / F;
-  const int mode = ih == p.zh[S] ? 2 : ih == 0 ? 1 : 0;  // 2: row zh folds into zh - 1; 1: -1 into 0
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const float* vj = v + HM + F * j;  // pixel px0 + F*j
-    float h = 0.f;
-#pragma unroll
-    for (int dd = -HF; dd < 3 * HF; ++dd) h += hat_w(dd, F) * vj[dd];
-    if (ix0 + j == 0) {  // virtual column -1 (pixels dd - F)
-#pragma unroll
-      for (int dd = F; dd < 3 * HF; ++dd) h += hat_w(dd, F) * vj[dd - F];
-    }
-    if (ix0 + j == zw - 1) {  // virtual column zw (pixels F*(j+1) + dd)
-#pragma unroll
-      for (int dd = -HF; dd < 0; ++dd) h += hat_w(dd, F) * vj[F + dd];
-    }
-    if (mode == 2) {
-      a.lo[j] += wh * h;
-      a.lo[j] += wl * h;
-    } else if (mode == 1) {
-      a.hi[j] += wh * h;
-      a.hi[j] += wl * h;
-    } else {
-      a.hi[j] += wh * h;
-      a.lo[j] += wl * h;
-    }
-  }
-}
-
-template <int NUP>
-__global__ __launch_bounds__(256) void up_adj3_kernel(UpAdj p, int br, int nband) {
-  constexpr int HM = 1 << (NUP - 1);  // row / pixel halo: HF of the coarsest source
-  constexpr int NV = 16 + 2 * HM;     // dy pixels per wave and row
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ncb = (p.C + 63) >> 6;
-  const int lb = xcd_remap_blocks(blockIdx.x, gridDim.x);
-  const int xb = lb % p.nxb;
-  int t = lb / p.nxb;
-  const int cbi = t % ncb;
-  t /= ncb;
-  const int band = t % nband, n = t / nband;
-  const int c = cbi * 64 + lane;
-  const bool cok = c < p.C;
-  const int b0 = band * br, b1 = b0 + br < p.H ? b0 + br : p.H;
-  const int ys = b0 - HM > 0 ? b0 - HM : 0, ye = b1 + HM < p.H ? b1 + HM : p.H;
-  const int px0 = xb * kUsXB + 16 * wave;
-  // One buffer resource per dy row (num_records = the row's bytes): pixels left of the row
-  // wrap to huge offsets and pixels right of it exceed the row, so both load 0 with no
-  // per-pixel test; pad channels use an offset past any row.
-  const uint32_t pstep = (uint32_t)p.dy_ps * 4u, rbytes = (uint32_t)p.W * pstep;
-  const uint32_t loff = cok ? (uint32_t)(px0 - HM) * pstep + 4u * (uint32_t)c : kOOB;
-  const float* img = p.dy + (int64_t)n * p.H * p.W * p.dy_ps;
-  auto load_row = [&](int oy, float* dst) {
-    const __amdgpu_buffer_rsrc_t dr = make_rsrc(img + (int64_t)oy * p.W * p.dy_ps, rbytes);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) dst[i] = load1(dr, loff + (uint32_t)i * pstep);
-  };
-  Adj3Src<0> a0;
-  Adj3Src<1> a1;
-  Adj3Src<2> a2;
-  a0.cur = (ys + 1) >> 1;
-  a1.cur = (ys + 2) >> 2;
-  a2.cur = (ys + 4) >> 3;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    a0.lo[j] = a0.hi[j] = 0.f;
-    if (j < 4) a1.lo[j] = a1.hi[j] = 0.f;
-    if (j < 2) a2.lo[j] = a2.hi[j] = 0.f;
-  }
-  float v[NV], nv[NV];
-  load_row(ys, v);
-  for (int oy = ys; oy < ye; ++oy) {
-    if (oy + 1 < ye) load_row(oy + 1, nv);
-    adj3_row<0, HM>(a0, v, oy, p, n, b0, b1, px0, c, cok);
-    if constexpr (NUP > 1) adj3_row<1, HM>(a1, v, oy, p, n, b0, b1, px0, c, cok);
-    if constexpr (NUP > 2) adj3_row<2, HM>(a2, v, oy, p, n, b0, b1, px0, c, cok);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = nv[i];
-  }
-  adj3_store<0>(a0, p, n, a0.cur - 1, b0, b1, px0, c, cok);
-  if constexpr (NUP > 1) adj3_store<1>(a1, p, n, a1.cur - 1, b0, b1, px0, c, cok);
-  if constexpr (NUP > 2) adj3_store<2>(a2, p, n, a2.cur - 1, b0, b1, px0, c, cok);
-}
-
-// The one-pass adjoint applies: exact 2^(s+1) ratios, 64-pixel chunks, rows addressable
-// with 32-bit buffer offsets.
-static bool adj_one_pass(const vae2_act* dyd, int n, const vae2_act* dxds) {
-  if (!g_adj_fused || n < 1 || dyd->w % kUsXB != 0 || dyd->w * dyd->ps * 4 >= (int64_t)kOOB)
-    return false;
-  for (int s = 0; s < n; ++s)
-    if (!act_ok(&dxds[s]) || dyd->w != dxds[s].w << (s + 1) || dyd->h != dxds[s].h << (s + 1))
-      return false;
-  return true;
-}
-
-// The fuse layers' power-of-two adjoints (resample.hip, vae2_upsample_bilinear_bwd_pow2)
-// through the one-pass kernel when its shape rules hold (targets of exactly 2 / 4 / 8, in
-// that order; 64-pixel chunks); -1 when they do not (the caller takes its two-pass path).
-int adj3_fuse_launch(const float* dy, const vae2_act* dyd, int n, float* const* dxs,
-                     const vae2_act* dxds, const float* betas, hipStream_t st) {
-  if (!g_adj_fused || !g_fuse_adj3 || n < 1 || n > 3 || !adj_one_pass(dyd, n, dxds)) return -1;
-  for (int s = 0; s < n; ++s)
-    if (!dxs[s] || dxds[s].n != dyd->n || dxds[s].c != dyd->c) return -1;
-  UpAdj p{};
-  p.dy = dy; p.dy_ps = (int)dyd->ps; p.H = (int)dyd->h; p.W = (int)dyd->w; p.C = (int)dyd->c;
-  for (int s = 0; s < n; ++s) {
-    p.dx[s] = dxs[s]; p.zh[s] = (int)dxds[s].h; p.zw[s] = (int)dxds[s].w;
-    p.dx_ps[s] = (int)dxds[s].ps;
-    p.beta[s] = betas ? betas[s] : 0.f;
-  }
-  p.nxb = (int)ceil_div(dyd->w, kUsXB);
-  const int br = dyd->h < g_adj_band ? (int)dyd->h : g_adj_band;
-  const int nband = (int)ceil_div(dyd->h, br);
-  const dim3 grid((unsigned)(dyd->n * nband * p.nxb * ceil_div(dyd->c, 64)));
-  switch (n) {
-    case 1: VAE2_LAUNCH(up_adj3_kernel<1>, grid, dim3(256), 0, st, p, br, nband); break;
-    case 2: VAE2_LAUNCH(up_adj3_kernel<2>, grid, dim3(256), 0, st, p, br, nband); break;
-    default: VAE2_LAUNCH(up_adj3_kernel<3>, grid, dim3(256), 0, st, p, br, nband); break;
-  }
-  return 0;
-}
-
 // Pixels per block of the backward passes (>= 64 each): the reduce pass with <= 2048
 // blocks (a block holds only 3 pixel rows of 68 channel quads, so 1024 blocks left one
 // wave per SIMD: 134 -> 122 us per head), the apply pass with <= 1024 (measured better).
@@ -1263,25 +734,55 @@ static bool head_args_ok(const float* y, const vae2_act* yd, int cout2) {
          cout2 >= 1 && cout2 <= kHeadMaxOut;
 }
 
-#define HEAD_DISPATCH(CO_, KERNEL, ...)                                   \
-  switch (CO_) {                                                          \
-    case 1: VAE2_LAUNCH((KERNEL<1>), __VA_ARGS__); break;          \
-    case 2: VAE2_LAUNCH((KERNEL<2>), __VA_ARGS__); break;          \
-    case 3: VAE2_LAUNCH((KERNEL<3>), __VA_ARGS__); break;          \
-    default: VAE2_LAUNCH((KERNEL<4>), __VA_ARGS__); break;         \
-  }
-// with U pixels in flight per thread (2 or 4)
-#define HEAD_DISPATCH_U(CO_, U_, KERNEL, ...)                                  \
-  if ((U_) == 4) {                                                             \
-    switch (CO_) {                                                             \
-      case 1: VAE2_LAUNCH((KERNEL<1, 4>), __VA_ARGS__); break;                 \
-      case 2: VAE2_LAUNCH((KERNEL<2, 4>), __VA_ARGS__); break;                 \
-      case 3: VAE2_LAUNCH((KERNEL<3, 4>), __VA_ARGS__); break;                 \
-      default: VAE2_LAUNCH((KERNEL<4, 4>), __VA_ARGS__); break;                \
-    }                                                                          \
-  } else {                                                                     \
-    HEAD_DISPATCH(CO_, KERNEL, __VA_ARGS__)                                    \
-  }
+// Kernel tables: [cout2 - 1] (1..4) [U == 4 pixels in flight]; [nup] (0..3) and the one-pass
+// up-sum's [cin4 / 4 - 1] K quads or the staged one's {tight KQ 5, tight KQ 8, wide KQ 8}.
+constexpr decltype(&head_out_fwd_kernel<1>) kHeadFwd[4] = {
+    head_out_fwd_kernel<1>, head_out_fwd_kernel<2>, head_out_fwd_kernel<3>,
+    head_out_fwd_kernel<4>};
+constexpr decltype(&head_out_bwd_reduce_kernel<1, 2>) kHeadReduce[4][2] = {
+    {head_out_bwd_reduce_kernel<1, 2>, head_out_bwd_reduce_kernel<1, 4>},
+    {head_out_bwd_reduce_kernel<2, 2>, head_out_bwd_reduce_kernel<2, 4>},
+    {head_out_bwd_reduce_kernel<3, 2>, head_out_bwd_reduce_kernel<3, 4>},
+    {head_out_bwd_reduce_kernel<4, 2>, head_out_bwd_reduce_kernel<4, 4>}};
+constexpr decltype(&head_out_bwd_apply_kernel<1, 2>) kHeadApply[4][2] = {
+    {head_out_bwd_apply_kernel<1, 2>, head_out_bwd_apply_kernel<1, 4>},
+    {head_out_bwd_apply_kernel<2, 2>, head_out_bwd_apply_kernel<2, 4>},
+    {head_out_bwd_apply_kernel<3, 2>, head_out_bwd_apply_kernel<3, 4>},
+    {head_out_bwd_apply_kernel<4, 2>, head_out_bwd_apply_kernel<4, 4>}};
+using UpSumKernel = void (*)(UpSum);
+template <int N>
+constexpr UpSumKernel kUpSum2Kq[5] = {upsum2_kernel<N, 1>, upsum2_kernel<N, 2>, upsum2_kernel<N, 3>,
+                                      upsum2_kernel<N, 4>, upsum2_kernel<N, 5>};
+constexpr const UpSumKernel* kUpSum2[4] = {kUpSum2Kq<0>, kUpSum2Kq<1>, kUpSum2Kq<2>, kUpSum2Kq<3>};
+template <int N>
+constexpr UpSumKernel kUpSumForm[3] = {upsum_kernel<N, true, 5>, upsum_kernel<N, true, 8>,
+                                       upsum_kernel<N, false, 8>};
+constexpr const UpSumKernel* kUpSum[4] = {kUpSumForm<0>, kUpSumForm<1>, kUpSumForm<2>,
+                                          kUpSumForm<3>};
+
+// vae2_heads_set_algo: a set bit stores `set`, a clear one `clear` (the default).
+struct Switch { int* var; int bit, clear, set; };
+static int g_upsum_tight = 1, g_upsum_one = 1, g_head_red_u = 2, g_head_app_u = 2;
+static const Switch kSwitches[] = {
+    // two-pass pow2 adjoint: vertical pass per channel lane (up_adj2_v), not streamed (_vs)
+    {&g_adj_stream, 1, 1, 0},
+    // the LDS-staged up-sum stages 12 columns per wave for every source, not 12 >> s
+    // (us_vu: 42 instead of 72 load / blend registers, 3 instead of 2 waves per SIMD)
+    {&g_upsum_tight, 2, 1, 0},
+    {&g_adj_fused, 4, 1, 0},  // no one-pass band adjoint (up_adj3_kernel): two passes instead
+    {&g_upsum_one, 8, 1, 0},  // no one-pass up-sum (upsum2_kernel): upsum_kernel everywhere
+    // 4 instead of 2 pixels in flight per thread in the backward reduce (2: 4 waves per
+    // SIMD, 120 -> 95 us per head in round 2) and in the backward apply
+    {&g_head_red_u, 16, 2, 4},
+    {&g_head_app_u, 32, 2, 4},
+    // the fuse adjoints (vae2_upsample_bilinear_bwd_pow2) through the one-pass band kernel.
+    // Off: with 18-72 channels a 64-lane channel block is mostly idle, and the step measured
+    // 851-853 vs 861-866 frames/s through the two-pass quad kernels (A/B, same box)
+    {&g_fuse_adj3, 64, 0, 1},
+    {&g_relu_dual_q, 128, 1, 0},  // relu_bwd_dual a channel per thread, not a channel quad
+};
+// Bits 8-15 (g_adj_band): dy rows per workgroup of the one-pass adjoint, a multiple of 8
+// from 8 up; any other value, 0 included, is the default, which reads back as 0.
 
 }  // namespace vae2
 
@@ -1301,8 +802,8 @@ int vae2_head_out_fwd(const float* y, const vae2_act* yd, const float* save, con
   const size_t shm = (size_t)(2 + cout2) * c4 * 16;
   const int64_t P = act_pixels(yd);
   const unsigned grid = (unsigned)(ceil_div(P, 16) < 8192 ? ceil_div(P, 16) : 8192);
-  HEAD_DISPATCH(cout2, head_out_fwd_kernel, dim3(grid), dim3(256), shm, as_stream(stream), y,
-                to_act(yd), save, w2, b2, out, to_act(outd));
+  VAE2_LAUNCH(kHeadFwd[cout2 - 1], dim3(grid), dim3(256), shm, as_stream(stream), y,
+              to_act(yd), save, w2, b2, out, to_act(outd));
   return check_launch(fn);
 }
 
@@ -1330,8 +831,8 @@ int vae2_head_out_bwd_reduce(const float* y, const vae2_act* yd, const float* sa
   const unsigned blocks = (unsigned)ceil_div(P, ppb);
   const size_t shm = ((size_t)rows * NC + (size_t)ppb * cout2) * sizeof(float);
   VAE2_REQUIRE(shm <= 64 * 1024, fn, "too many channels for the LDS reduction");
-  HEAD_DISPATCH_U(cout2, g_head_red_u, head_out_bwd_reduce_kernel, dim3(blocks), dim3(256), shm,
-                as_stream(stream), y, to_act(yd), save, w2, dout, to_act(doutd), ppb, rows, ws);
+  VAE2_LAUNCH(kHeadReduce[cout2 - 1][g_head_red_u == 4], dim3(blocks), dim3(256), shm,
+              as_stream(stream), y, to_act(yd), save, w2, dout, to_act(doutd), ppb, rows, ws);
   int rc = check_launch(fn);
   if (rc) return rc;
   VAE2_LAUNCH(head_bwd_colsum_kernel, dim3((unsigned)ceil_div(NC, 64)), dim3(1024), 0,
@@ -1357,9 +858,9 @@ int vae2_head_out_bwd_apply(const float* y, const vae2_act* yd, const float* sav
   const int64_t P = act_pixels(yd), ppb = head_ppb(P, 1024);
   const unsigned blocks = (unsigned)ceil_div(P, ppb);
   const size_t shm = ((size_t)rows * C + (size_t)ppb * cout2) * sizeof(float);
-  HEAD_DISPATCH_U(cout2, g_head_app_u, head_out_bwd_apply_kernel, dim3(blocks), dim3(256), shm,
-                as_stream(stream), y, to_act(yd), save, gamma, w2, dout, to_act(doutd), sums,
-                count, ppb, rows, dy, to_act(dyd), ws);
+  VAE2_LAUNCH(kHeadApply[cout2 - 1][g_head_app_u == 4], dim3(blocks), dim3(256), shm,
+              as_stream(stream), y, to_act(yd), save, gamma, w2, dout, to_act(doutd), sums,
+              count, ppb, rows, dy, to_act(dyd), ws);
   int rc = check_launch(fn);
   if (rc) return rc;
   if (dbias) return bias_grad_from_partials(ws, blocks, C, dbias, 1, stream);
@@ -1420,162 +921,25 @@ int vae2_conv1x1_upsum_fwd(const float* x, const vae2_act* xd, const float* wp,
   for (int s = 0; s < nup; ++s)
     one = one && yd->h == (int64_t)p.zh[s] << (s + 1) && yd->w == (int64_t)p.zw[s] << (s + 1);
   if (one) {
-#define US2_LAUNCH(N)                                                                   \
-  switch (p.cin4 / 4) {                                                                 \
-    case 1: VAE2_LAUNCH((upsum2_kernel<N, 1>), grid, dim3(256), 0, st, p); break;       \
-    case 2: VAE2_LAUNCH((upsum2_kernel<N, 2>), grid, dim3(256), 0, st, p); break;       \
-    case 3: VAE2_LAUNCH((upsum2_kernel<N, 3>), grid, dim3(256), 0, st, p); break;       \
-    case 4: VAE2_LAUNCH((upsum2_kernel<N, 4>), grid, dim3(256), 0, st, p); break;       \
-    default: VAE2_LAUNCH((upsum2_kernel<N, 5>), grid, dim3(256), 0, st, p); break;      \
-  }
-    switch (nup) {
-      case 0: US2_LAUNCH(0) break;
-      case 1: US2_LAUNCH(1) break;
-      case 2: US2_LAUNCH(2) break;
-      default: US2_LAUNCH(3) break;
-    }
-#undef US2_LAUNCH
+    VAE2_LAUNCH(kUpSum2[nup][p.cin4 / 4 - 1], grid, dim3(256), 0, st, p);
     return check_launch(fn);
   }
   bool tight = g_upsum_tight != 0;
   for (int s = 0; s < nup; ++s) tight = tight && p.vcols[s] <= 4 * us_vu(s, true);
-  const bool kq5 = p.cin4 <= 20;
-#define US_LAUNCH(N)                                                                    \
-  if (tight && kq5) VAE2_LAUNCH((upsum_kernel<N, true, 5>), grid, dim3(256), shm, st, p); \
-  else if (tight) VAE2_LAUNCH((upsum_kernel<N, true, 8>), grid, dim3(256), shm, st, p); \
-  else VAE2_LAUNCH((upsum_kernel<N, false, 8>), grid, dim3(256), shm, st, p);
-  switch (nup) {
-    case 0: US_LAUNCH(0) break;
-    case 1: US_LAUNCH(1) break;
-    case 2: US_LAUNCH(2) break;
-    default: US_LAUNCH(3) break;
-  }
-#undef US_LAUNCH
+  const int form = !tight ? 2 : p.cin4 <= 20 ? 0 : 1;
+  VAE2_LAUNCH(kUpSum[nup][form], grid, dim3(256), shm, st, p);
   return check_launch(fn);
 }
 
-int64_t vae2_upsample_bilinear_bwd_multi_ws_size(const vae2_act* dyd, int n,
-                                                 const vae2_act* dxds) {
-  if (!act_ok(dyd) || n < 0 || n > 3 || (n && !dxds)) return 0;
-  if (adj_one_pass(dyd, n, dxds)) return 1;  // no hb intermediate
-  int64_t t = 0;
-  for (int s = 0; s < n; ++s) t += dyd->n * dyd->h * dxds[s].w * dyd->c;
-  return t > 0 ? t : 1;
-}
-
 int vae2_heads_set_algo(int algo) {
-  const int prev = (g_adj_stream ? 0 : 1) | (g_upsum_tight ? 0 : 2) | (g_adj_fused ? 0 : 4) |
-                   (g_upsum_one ? 0 : 8) | (g_head_red_u == 4 ? 16 : 0) |
-                   (g_head_app_u == 4 ? 32 : 0) | (g_fuse_adj3 ? 64 : 0) |
-                   (g_relu_dual_q ? 0 : 128) | (g_adj_band == 32 ? 0 : g_adj_band << 8);
-  g_adj_stream = (algo & 1) ? 0 : 1;
-  g_upsum_tight = (algo & 2) ? 0 : 1;
-  g_adj_fused = (algo & 4) ? 0 : 1;
-  g_upsum_one = (algo & 8) ? 0 : 1;
-  g_head_red_u = (algo & 16) ? 4 : 2;
-  g_head_app_u = (algo & 32) ? 4 : 2;
-  g_fuse_adj3 = (algo & 64) ? 1 : 0;
-  g_relu_dual_q = (algo & 128) ? 0 : 1;
-  const int band = (algo >> 8) & 0xff;  // one-pass adjoint band rows (0: default 32)
-  g_adj_band = band >= 8 && band % 8 == 0 ? band : 32;
+  int prev = g_adj_band == kAdjBandDefault ? 0 : g_adj_band << 8;
+  for (const Switch& sw : kSwitches) {
+    if (*sw.var == sw.set) prev |= sw.bit;
+    *sw.var = (algo & sw.bit) ? sw.set : sw.clear;
+  }
+  const int band = (algo >> 8) & 0xff;
+  g_adj_band = band >= 8 && band % 8 == 0 ? band : kAdjBandDefault;
   return prev;
-}
-
-int vae2_upsample_bilinear_bwd_multi(const float* dy, const vae2_act* dyd, int n,
-                                     float* const* dxs, const vae2_act* dxds, float* ws,
-                                     int64_t ws_size, void* stream) {
-  const char* fn = "vae2_upsample_bilinear_bwd_multi";
-  VAE2_REQUIRE(dy && act_ok(dyd) && n >= 0 && n <= 3 && (n == 0 || (dxs && dxds)) && ws, fn,
-               "bad arguments");
-  VAE2_REQUIRE(ws_size >= vae2_upsample_bilinear_bwd_multi_ws_size(dyd, n, dxds), fn,
-               "workspace too small");
-  if (n == 0) return 0;
-  UpAdj p{};
-  p.dy = dy; p.dy_ps = (int)dyd->ps; p.H = (int)dyd->h; p.W = (int)dyd->w; p.C = (int)dyd->c;
-  float* hb = ws;
-  float min_sw = 1.f;
-  for (int s = 0; s < n; ++s) {
-    const vae2_act* d = &dxds[s];
-    VAE2_REQUIRE(dxs[s] && act_ok(d) && d->n == dyd->n && d->c == dyd->c && d->h <= dyd->h &&
-                     d->w <= dyd->w, fn, "dx shape mismatch");
-    p.dx[s] = dxs[s]; p.zh[s] = (int)d->h; p.zw[s] = (int)d->w; p.dx_ps[s] = (int)d->ps;
-    p.sh[s] = (float)d->h / (float)dyd->h;
-    p.sw[s] = (float)d->w / (float)dyd->w;
-    VAE2_REQUIRE(2.f / p.sh[s] + 6.f <= 64.f, fn, "upsampling ratio too large (> 24)");
-    if (p.sw[s] < min_sw) min_sw = p.sw[s];
-    p.hb[s] = hb;
-    hb += dyd->n * dyd->h * d->w * dyd->c;
-  }
-  p.nxb = (int)ceil_div(dyd->w, kUsXB);
-  const unsigned cb = (unsigned)ceil_div(dyd->c, 64);
-  hipStream_t st = as_stream(stream);
-  bool pow2 = dyd->w % kUsXB == 0;
-  for (int s = 0; s < n; ++s)
-    pow2 = pow2 && dyd->w == (int64_t)p.zw[s] << (s + 1) && dyd->h == (int64_t)p.zh[s] << (s + 1);
-  if (adj_one_pass(dyd, n, dxds)) {
-    const int br = dyd->h < g_adj_band ? (int)dyd->h : g_adj_band;
-    const int nband = (int)ceil_div(dyd->h, br);
-    const dim3 grid((unsigned)(dyd->n * nband * p.nxb * cb));
-    switch (n) {
-      case 1: VAE2_LAUNCH(up_adj3_kernel<1>, grid, dim3(256), 0, st, p, br, nband); break;
-      case 2: VAE2_LAUNCH(up_adj3_kernel<2>, grid, dim3(256), 0, st, p, br, nband); break;
-      default: VAE2_LAUNCH(up_adj3_kernel<3>, grid, dim3(256), 0, st, p, br, nband); break;
-    }
-    return check_launch(fn);
-  }
-  if (pow2) {
-    const dim3 grid((unsigned)(dyd->n * dyd->h * p.nxb * cb));
-    switch (n) {
-      case 1: VAE2_LAUNCH(up_adj2_h_kernel<1>, grid, dim3(256), 0, st, p); break;
-      case 2: VAE2_LAUNCH(up_adj2_h_kernel<2>, grid, dim3(256), 0, st, p); break;
-      default: VAE2_LAUNCH(up_adj2_h_kernel<3>, grid, dim3(256), 0, st, p); break;
-    }
-    int rc = check_launch(fn);
-    if (rc) return rc;
-    for (int s = 0; s < n; ++s) {
-      const int64_t rs = (int64_t)p.zw[s] * p.C;
-      if (rs % 4 == 0 && g_adj_stream) {
-        const int64_t nq = rs / 4;
-        const dim3 gv((unsigned)(dyd->n * p.zh[s]), (unsigned)ceil_div(nq, 512));
-        const FastDiv cdiv((uint32_t)p.C);
-        switch (s) {
-          case 0: VAE2_LAUNCH(up_adj2_vs_kernel<0>, gv, dim3(256), 0, st, p, cdiv); break;
-          case 1: VAE2_LAUNCH(up_adj2_vs_kernel<1>, gv, dim3(256), 0, st, p, cdiv); break;
-          default: VAE2_LAUNCH(up_adj2_vs_kernel<2>, gv, dim3(256), 0, st, p, cdiv); break;
-        }
-      } else {
-        const dim3 gv((unsigned)(dyd->n * p.zh[s]), cb);
-        switch (s) {
-          case 0: VAE2_LAUNCH(up_adj2_v_kernel<0>, gv, dim3(256), 0, st, p); break;
-          case 1: VAE2_LAUNCH(up_adj2_v_kernel<1>, gv, dim3(256), 0, st, p); break;
-          default: VAE2_LAUNCH(up_adj2_v_kernel<2>, gv, dim3(256), 0, st, p); break;
-        }
-      }
-      rc = check_launch(fn);
-      if (rc) return rc;
-    }
-    return 0;
-  }
-  // halo: the owned columns' windows reach at most 1/sw + 3 pixels past the chunk
-  p.halo = (int)ceilf(1.f / min_sw) + 4;
-  const int span = kUsXB + 2 * p.halo;
-  const size_t shm = (size_t)(4 * n + 64) * span * sizeof(float);
-  VAE2_REQUIRE(shm <= 64 * 1024, fn, "upsampling ratio too large for the LDS tile");
-  dim3 grid((unsigned)(dyd->n * dyd->h * p.nxb * cb));
-  switch (n) {
-    case 1: VAE2_LAUNCH(up_adj_h_kernel<1>, grid, dim3(256), shm, st, p); break;
-    case 2: VAE2_LAUNCH(up_adj_h_kernel<2>, grid, dim3(256), shm, st, p); break;
-    default: VAE2_LAUNCH(up_adj_h_kernel<3>, grid, dim3(256), shm, st, p); break;
-  }
-  int rc = check_launch(fn);
-  if (rc) return rc;
-  for (int s = 0; s < n; ++s) {
-    VAE2_LAUNCH(up_adj_v_kernel, dim3((unsigned)(dyd->n * p.zh[s]), cb), dim3(256), 0, st,
-                       p, s);
-    rc = check_launch(fn);
-    if (rc) return rc;
-  }
-  return 0;
 }
 
 }  // extern "C"

@@ -1,69 +1,18 @@
-// Bilinear resampling, multi-resolution fuse sums, code-map tiling, layout
-// conversion and global average pooling for NHWC fp32 activations.
+// Bilinear resampling forward and its single-target adjoint, multi-resolution fuse sums,
+// ReLU backward, copies, code-map tiling, spatial sums (global / weighted average
+// pooling) and layout conversion for NHWC fp32 activations.
 //
 //   F.interpolate / F.upsample(mode='bilinear', align_corners=False)
-//       enc_hrnet.py:242-245 (fuse), :835-837 / :893-895 / :951-953 (heads),
-//       :1111-1113 (z-net)                              -> upsample fwd / bwd
-//   HighResolutionModule fuse sum + ReLU :233-249      -> fuse_sum_relu
+//       enc_hrnet.py:242-245 (fuse), :1111-1113 (z-net)  -> upsample fwd / bwd
+//       (the adjoints into several targets at once: upadj.hip)
+//   HighResolutionModule fuse sum + ReLU :233-249      -> fuse_sum_relu, relu_bwd(_dual)
 //   _gen_code_map + torch.cat :454-462, :819-827       -> codemap tile fwd / bwd
 //   nn.AdaptiveAvgPool2d((1,1)) :1025                  -> global avgpool fwd / bwd
-#include "common.h"
-
-#include <cxxabi.h>
-
-#include <atomic>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "heads.h"
 
 namespace vae2 {
 
-// ------------------------------------------------------ launch log ----
-static std::atomic<bool> g_klog{false};
-static thread_local std::vector<const void*> g_klog_v;
-
-void note_kernel(const void* host_fn) {
-  if (g_klog.load(std::memory_order_relaxed)) g_klog_v.push_back(host_fn);
-}
-
-// "void vae2::dconv3_kernel<4, 2, false>(vae2::DConv)" -> "dconv3_kernel<4, 2, false>"
-static std::string kernel_label(const void* fn) {
-  const char* raw = hipKernelNameRefByPtr(fn, nullptr);
-  if (!raw) return "?";
-  int st = 0;
-  char* dem = abi::__cxa_demangle(raw, nullptr, nullptr, &st);
-  std::string s = (st == 0 && dem) ? dem : raw;
-  std::free(dem);
-  if (s.rfind("void ", 0) == 0) s = s.substr(5);
-  int depth = 0;
-  for (size_t i = 0; i < s.size(); ++i) {  // drop the parameter list
-    if (s[i] == '<') ++depth;
-    if (s[i] == '>') --depth;
-    if (s[i] == '(' && depth == 0) { s = s.substr(0, i); break; }
-  }
-  size_t pos;
-  while ((pos = s.find("vae2::")) != std::string::npos) s.erase(pos, 6);
-  return s;
-}
-
-// ------------------------------------------------------------- errors ----
-static thread_local std::string g_last_error;
-
-void set_error(const std::string& msg) { g_last_error = msg; }
-
-int fail(const char* fn, const std::string& msg) {
-  set_error(std::string(fn) + ": " + msg);
-  return -22;
-}
-
-int check_launch(const char* fn) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string(fn) + ": " + hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
+int g_relu_dual_q = 1;  // heads.h: the quad form of relu_bwd_dual (kSwitches, heads.hip)
 
 // ------------------------------------------------- bilinear helpers ----
 // (lerp_index: common.h)
@@ -155,7 +104,6 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restri
 // computed once per thread instead of once per (row, column).  Same summation order
 // as upsample_bwd_kernel (row sums over ascending columns, then rows).  Windows wider
 // than kUpW columns take the generic loop.
-typedef float f4v __attribute__((ext_vector_type(4)));
 constexpr int kUpW = 24;
 
 __global__ __launch_bounds__(256) void upsample_bwd4_kernel(const float* __restrict__ dy, Act dyd,
@@ -187,7 +135,7 @@ __global__ __launch_bounds__(256) void upsample_bwd4_kernel(const float* __restr
     if (iy == (int)dxd.h - 1) yhi = OH - 1;
     if (ix == (int)dxd.w - 1) xhi = OW - 1;
     const float* base = dy + (int64_t)n * OH * OW * ps + c;
-    f4v acc = {0.f, 0.f, 0.f, 0.f};
+    f4 acc = {0.f, 0.f, 0.f, 0.f};
     if (xhi - xlo < kUpW) {
       float wx[kUpW];
 #pragma unroll
@@ -197,21 +145,21 @@ __global__ __launch_bounds__(256) void upsample_bwd4_kernel(const float* __restr
         const float wy = lerp_weight(oy, (int)dxd.h, sh, iy);
         if (wy == 0.f) continue;
         const float* rp = base + ((int64_t)oy * OW + xlo) * ps;
-        f4v ax = {0.f, 0.f, 0.f, 0.f};
+        f4 ax = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int k = 0; k < kUpW; ++k)
-          if (wx[k] != 0.f) ax += wx[k] * *reinterpret_cast<const f4v*>(rp + k * ps);
+          if (wx[k] != 0.f) ax += wx[k] * *reinterpret_cast<const f4*>(rp + k * ps);
         acc += wy * ax;
       }
     } else {
       for (int oy = ylo; oy <= yhi; ++oy) {
         const float wy = lerp_weight(oy, (int)dxd.h, sh, iy);
         if (wy == 0.f) continue;
-        f4v ax = {0.f, 0.f, 0.f, 0.f};
+        f4 ax = {0.f, 0.f, 0.f, 0.f};
         for (int ox = xlo; ox <= xhi; ++ox) {
           const float wxv = lerp_weight(ox, (int)dxd.w, sw, ix);
           if (wxv == 0.f) continue;
-          ax += wxv * *reinterpret_cast<const f4v*>(base + ((int64_t)oy * OW + ox) * ps);
+          ax += wxv * *reinterpret_cast<const f4*>(base + ((int64_t)oy * OW + ox) * ps);
         }
         acc += wy * ax;
       }
@@ -221,89 +169,6 @@ __global__ __launch_bounds__(256) void upsample_bwd4_kernel(const float* __restr
     for (int k = 0; k < 4; ++k)
       if (c + k < C) dst[k] = (beta != 0.f) ? acc[k] + beta * dst[k] : acc[k];
   }
-}
-
-// The adjoint for up to 3 targets at exact 2, 4, 8 ratios (a fuse row's lower branches),
-// one thread per (pixel, channel quad) so that narrow layers (18 channels) keep every
-// lane busy: a horizontal pass of all targets (one launch) into a quad-padded workspace
-// hb[s] = [n][H][zw][4Q], then a vertical pass of all targets (one launch), both with the
-// static hat stencils.  dy is read once from HBM; hb (1/F of dy each) twice from L2.
-struct UpAdjQ {
-  const float* g;
-  int64_t g_ps;
-  int H, W, Q, C, nt;
-  float* hb[3];
-  float* dx[3];
-  int64_t dx_ps[3];
-  int zh[3], zw[3], lf[3];  // lf = log2 of the ratio (1..3)
-  float beta[3];
-  uint32_t cnt_h[3], cnt_v[3];
-  FastDiv zwq[3], zh_d[3], q_d;
-};
-
-// sum_d hat_w(d, F) v[F*i + d] over a line of `len` points with stride `st`, edges folded.
-// Every tap's load is unconditional (out-of-line taps read a clamped in-line point with
-// weight 0): guarded loads were branched around one by one, each waited for in turn.
-template <int F>
-__device__ __forceinline__ f4v hat_adj(const float* line, int64_t st, int len, int i, int n_src) {
-  constexpr int HF = F / 2;
-  const int x0 = F * i;
-  f4v v[4 * HF];
-#pragma unroll
-  for (int d = -HF; d < 3 * HF; ++d) {
-    const int x = x0 + d;
-    const int xc = x < 0 ? 0 : (x >= len ? len - 1 : x);
-    v[d + HF] = *reinterpret_cast<const f4v*>(line + xc * st);
-  }
-  f4v acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int d = -HF; d < 3 * HF; ++d) {
-    const int x = x0 + d;
-    if (x >= 0 && x < len) acc += hat_w(d, F) * v[d + HF];
-  }
-  if (i == 0) {  // virtual source -1: points d - F
-#pragma unroll
-    for (int d = F; d < 3 * HF; ++d)
-      acc += hat_w(d, F) * *reinterpret_cast<const f4v*>(line + (d - F) * st);
-  }
-  if (i == n_src - 1) {  // virtual source n_src: points len + d
-#pragma unroll
-    for (int d = -HF; d < 0; ++d)
-      acc += hat_w(d, F) * *reinterpret_cast<const f4v*>(line + (len + d) * st);
-  }
-  return acc;
-}
-
-template <bool VERT>
-__global__ __launch_bounds__(256) void up_adjq_kernel(UpAdjQ p) {
-  const int s = blockIdx.y;
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= (VERT ? p.cnt_v[s] : p.cnt_h[s])) return;
-  const int zw = p.zw[s], Q = p.Q, lf = p.lf[s];
-  const uint32_t row = p.zwq[s].div(i);  // horizontal: n*H + oy; vertical: n*zh + iy
-  const uint32_t r = i - row * (uint32_t)(zw * Q);
-  const uint32_t ix = p.q_d.div(r);
-  const uint32_t q = r - ix * (uint32_t)Q;
-  const int64_t hrow = (int64_t)zw * 4 * Q;  // hb row stride
-  if (!VERT) {
-    const float* line = p.g + (int64_t)row * p.W * p.g_ps + 4 * q;
-    const f4v acc = lf == 1   ? hat_adj<2>(line, p.g_ps, p.W, (int)ix, zw)
-                    : lf == 2 ? hat_adj<4>(line, p.g_ps, p.W, (int)ix, zw)
-                              : hat_adj<8>(line, p.g_ps, p.W, (int)ix, zw);
-    *reinterpret_cast<f4v*>(p.hb[s] + (int64_t)row * hrow + 4 * (ix * Q + q)) = acc;
-    return;
-  }
-  const uint32_t n = p.zh_d[s].div(row);
-  const int iy = (int)(row - n * (uint32_t)p.zh[s]);
-  const float* line = p.hb[s] + (int64_t)n * p.H * hrow + 4 * (ix * Q + q);
-  const f4v acc = lf == 1   ? hat_adj<2>(line, hrow, p.H, iy, p.zh[s])
-                  : lf == 2 ? hat_adj<4>(line, hrow, p.H, iy, p.zh[s])
-                            : hat_adj<8>(line, hrow, p.H, iy, p.zh[s]);
-  float* dst = p.dx[s] + ((int64_t)row * zw + ix) * p.dx_ps[s] + 4 * q;
-  const float beta = p.beta[s];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if ((int)(4 * q) + k < p.C) dst[k] = (beta != 0.f) ? acc[k] + beta * dst[k] : acc[k];
 }
 
 struct FuseTerms {
@@ -715,41 +580,11 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restri
   }
 }
 
-static bool same_hw(const vae2_act* a, const vae2_act* b) {
-  return a->n == b->n && a->h == b->h && a->w == b->w;
-}
-
 }  // namespace vae2
 
 using namespace vae2;
 
 extern "C" {
-
-int vae2_abi_version(void) { return VAE2_ABI_VERSION; }
-
-const char* vae2_last_error(void) { return g_last_error.c_str(); }
-
-int vae2_kernel_log(int enable) {
-  g_klog.store(enable != 0);
-  g_klog_v.clear();
-  return 0;
-}
-
-int64_t vae2_kernel_log_read(char* buf, int64_t len) {
-  std::string out;
-  for (size_t i = 0; i < g_klog_v.size(); ++i) {
-    if (i) out += ';';
-    out += kernel_label(g_klog_v[i]);
-  }
-  const int64_t n = (int64_t)g_klog_v.size();
-  g_klog_v.clear();
-  if (buf && len > 0) {
-    const size_t m = out.size() < (size_t)(len - 1) ? out.size() : (size_t)(len - 1);
-    std::memcpy(buf, out.data(), m);
-    buf[m] = 0;
-  }
-  return n;
-}
 
 int vae2_upsample_bilinear_fwd(const float* x, const vae2_act* xd, float* y,
                                const vae2_act* yd, float beta, void* stream) {
@@ -785,71 +620,6 @@ int vae2_upsample_bilinear_bwd(const float* dy, const vae2_act* dyd, float* dx,
                      as_stream(stream), dy, to_act(dyd), dx, to_act(dxd), beta,
                      FastDiv((uint32_t)dxd->c), FastDiv((uint32_t)dxd->w),
                      FastDiv((uint32_t)dxd->h));
-  return check_launch(fn);
-}
-
-// log2 of an exact power-of-two ratio in {2, 4, 8}, else 0.
-static int pow2_ratio(int64_t big, int64_t small) {
-  for (int k = 1; k <= 3; ++k)
-    if (big == small << k) return k;
-  return 0;
-}
-
-int64_t vae2_upsample_bilinear_bwd_pow2_ws_size(const vae2_act* dyd, int n,
-                                                const vae2_act* dxds) {
-  if (!act_ok(dyd) || n < 1 || n > 3 || !dxds) return -1;
-  const int64_t Q = (dyd->c + 3) / 4;
-  int64_t t = 0;
-  for (int s = 0; s < n; ++s) {
-    const vae2_act* d = &dxds[s];
-    const int k = pow2_ratio(dyd->w, d->w);
-    if (!act_ok(d) || !k || pow2_ratio(dyd->h, d->h) != k || d->n != dyd->n || d->c != dyd->c)
-      return -1;
-    t += dyd->n * dyd->h * d->w * 4 * Q;
-  }
-  return t;
-}
-
-int vae2_upsample_bilinear_bwd_pow2(const float* dy, const vae2_act* dyd, int n,
-                                    float* const* dxs, const vae2_act* dxds,
-                                    const float* betas, float* ws, int64_t ws_size,
-                                    void* stream) {
-  const char* fn = "vae2_upsample_bilinear_bwd_pow2";
-  VAE2_REQUIRE(dy && act_ok(dyd) && n >= 1 && n <= 3 && dxs && dxds && ws, fn,
-               "bad arguments");
-  const int64_t need = vae2_upsample_bilinear_bwd_pow2_ws_size(dyd, n, dxds);
-  VAE2_REQUIRE(need >= 0, fn, "targets are not exact 2 / 4 / 8 downsamplings of dy");
-  VAE2_REQUIRE(ws_size >= need, fn, "workspace too small");
-  VAE2_REQUIRE(dyd->ps % 4 == 0 && (uintptr_t)dy % 16 == 0 && (uintptr_t)ws % 16 == 0, fn,
-               "dy and ws must be 16-byte aligned with a pixel stride of 4k");
-  hipStream_t st = as_stream(stream);
-  // one launch, dy read once (heads.hip's band kernel) where the targets are 2 / 4 / 8 in
-  // order and the rows are 64-pixel chunks
-  if (adj3_fuse_launch(dy, dyd, n, dxs, dxds, betas, st) == 0) return check_launch(fn);
-  UpAdjQ p{};
-  p.g = dy; p.g_ps = dyd->ps; p.H = (int)dyd->h; p.W = (int)dyd->w; p.C = (int)dyd->c;
-  p.Q = (p.C + 3) / 4; p.nt = n; p.q_d = FastDiv((uint32_t)p.Q);
-  float* hb = ws;
-  uint32_t mh = 0, mv = 0;
-  for (int s = 0; s < n; ++s) {
-    const vae2_act* d = &dxds[s];
-    VAE2_REQUIRE(dxs[s], fn, "null target");
-    const int64_t ch = dyd->n * dyd->h * d->w * p.Q, cv = dyd->n * d->h * d->w * p.Q;
-    VAE2_REQUIRE(ch < (int64_t(1) << 31), fn, "tensor too large");
-    p.dx[s] = dxs[s]; p.dx_ps[s] = d->ps; p.zh[s] = (int)d->h; p.zw[s] = (int)d->w;
-    p.lf[s] = pow2_ratio(dyd->w, d->w);
-    p.beta[s] = betas ? betas[s] : 0.f;
-    p.cnt_h[s] = (uint32_t)ch; p.cnt_v[s] = (uint32_t)cv;
-    p.zwq[s] = FastDiv((uint32_t)(d->w * p.Q)); p.zh_d[s] = FastDiv((uint32_t)d->h);
-    p.hb[s] = hb;
-    hb += dyd->n * dyd->h * d->w * 4 * p.Q;
-    if (p.cnt_h[s] > mh) mh = p.cnt_h[s];
-    if (p.cnt_v[s] > mv) mv = p.cnt_v[s];
-  }
-  VAE2_LAUNCH(up_adjq_kernel<false>, dim3((mh + 255) / 256, n), dim3(256), 0, st, p);
-  int rc = check_launch(fn);
-  if (rc) return rc;
-  VAE2_LAUNCH(up_adjq_kernel<true>, dim3((mv + 255) / 256, n), dim3(256), 0, st, p);
   return check_launch(fn);
 }
 
@@ -907,7 +677,7 @@ int vae2_relu_bwd(const float* dy, const vae2_act* dyd, const float* y,
                   void* stream) {
   const char* fn = "vae2_relu_bwd";
   VAE2_REQUIRE(dy && y && g && act_ok(dyd) && act_ok(yd) && act_ok(gd), fn, "bad arguments");
-  VAE2_REQUIRE(same_hw(dyd, yd) && same_hw(yd, gd) && dyd->c == yd->c && gd->c == yd->c, fn,
+  VAE2_REQUIRE(same_nhw(dyd, yd) && same_nhw(yd, gd) && dyd->c == yd->c && gd->c == yd->c, fn,
                "shape mismatch");
   VAE2_REQUIRE(idx32_ok(yd), fn, kTooLarge);
   int64_t total = act_elems(yd);
@@ -922,7 +692,7 @@ int vae2_relu_bwd_dual(const float* dy, const vae2_act* dyd, const float* y,
   const char* fn = "vae2_relu_bwd_dual";
   VAE2_REQUIRE(dy && y && g && g2 && act_ok(dyd) && act_ok(yd) && act_ok(gd) && act_ok(g2d),
                fn, "bad arguments");
-  VAE2_REQUIRE(same_hw(dyd, yd) && same_hw(yd, gd) && same_hw(yd, g2d) && dyd->c == yd->c &&
+  VAE2_REQUIRE(same_nhw(dyd, yd) && same_nhw(yd, gd) && same_nhw(yd, g2d) && dyd->c == yd->c &&
                    gd->c == yd->c && g2d->c == yd->c, fn, "shape mismatch");
   VAE2_REQUIRE(idx32_ok(yd), fn, kTooLarge);
   int64_t total = act_elems(yd);
@@ -946,7 +716,7 @@ int vae2_copy_act(const float* x, const vae2_act* xd, float* y,
                   const vae2_act* yd, float beta, void* stream) {
   const char* fn = "vae2_copy_act";
   VAE2_REQUIRE(x && y && act_ok(xd) && act_ok(yd), fn, "bad arguments");
-  VAE2_REQUIRE(same_hw(xd, yd) && xd->c == yd->c, fn, "shape mismatch");
+  VAE2_REQUIRE(same_nhw(xd, yd) && xd->c == yd->c, fn, "shape mismatch");
   VAE2_REQUIRE(idx32_ok(xd), fn, kTooLarge);
   int64_t total = act_elems(xd);
   VAE2_LAUNCH(copy_act_kernel, dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream),
